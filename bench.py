@@ -15,13 +15,18 @@ Other BASELINE.json configs (--config):
   celebahq256  C5: CelebA-HQ 256 (5 bits, 4 scales), batch 4 per GPU
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--config C] [--global-batch G]
+                    [--dump-outputs DIR] [--full]
 
 `--gpus N` (N > 1) without a torch.distributed launcher starts N rank processes (torch.distributed.run, one rank
 per GPU, RCCL) before anything touches the GPU and exits with their status; with fewer than N devices the ranks
 share them over gloo (a rehearsal).  Under torch.distributed.run (WORLD_SIZE set) each process is one rank.
 
-Prints one JSON line on rank 0 (metric, value = samples/s over all ranks, roofline of the
-dominant kernel measured live with HIP events, cpu_baseline = the oracle on the host cores).
+A plain run sets up, warms up, times the K steps and prints one JSON line on rank 0 (metric, value = samples/s
+over all ranks, ms_per_step).  `--dump-outputs DIR` also writes what the last timed step returned (rank 0's
+log p(x) per sample, z and the loss) as DIR/<name>.npy; with the same arguments the inputs, weights and probes are
+the same from run to run, so two builds can be compared output for output.  `--full` adds everything that takes
+runs of its own to the line: roofline and path (the dominant kernel and the HBM-bound phases, measured live with
+HIP events in one extra profiling step) and cpu_baseline (the oracle on the host cores, `--cpu-baseline 0` skips it).
 """
 import argparse
 import hashlib
@@ -126,7 +131,13 @@ def parse():
                     help='samples over all ranks (per-GPU batch = G / N); cifar10_c4 defaults to 2048')
     ap.add_argument('--config', default='cifar10', choices=sorted(BENCH_CONFIGS))
     ap.add_argument('--probes', default='device', choices=['device', 'reference'])
-    ap.add_argument('--cpu-baseline', type=int, default=1, help='time the oracle on the host (rank 0, N=1)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also run the per-kernel profiling step (roofline, path) and the CPU '
+                         'baseline (cpu_baseline, the delta against the oracle); a plain run does neither')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write what the last timed step returned as DIR/<name>.npy (rank 0; at most 64 MB in all)')
+    ap.add_argument('--cpu-baseline', type=int, default=1,
+                    help='with --full: time the oracle on the host (rank 0, N=1)')
     ap.add_argument('--cpu-batch', type=int, default=64,
                     help='images per timed CPU-baseline batch (BASELINE.md:36-38: B = 64; one warm-up batch of 8, then '
                          'the median of --cpu-reps batches).  Per-sample CPU time is NOT batch-independent on the GPU '
@@ -289,6 +300,25 @@ def cpu_baseline(arch, sd, model, device, nimg, reps=3, training=False):
             abs(float(gpu_loss) - float(ref_loss)), float(ref_loss))
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array as path/<name>.npy (float32 / float64 as computed), at most DUMP_LIMIT_BYTES in
+    all: an array over its even share of the limit is cut to a fixed seeded sample of its flattened values (the same
+    positions in every run, in ascending order)."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // len(arrays)
+    for name, t in arrays.items():
+        a = t.detach().to('cpu').numpy() if torch.is_tensor(t) else np.asarray(t)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        if a.nbytes > share:
+            keep = np.sort(np.random.RandomState(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[keep]
+        np.save(os.path.join(path, name + '.npy'), a)
+
+
 def spawn_ranks(args):
     """`--gpus N` without a launcher: one rank per GPU through torch.distributed.run (started before this process
     touches the GPU; counting devices does not initialise it), returning the ranks' exit status.  RCCL when there
@@ -363,11 +393,14 @@ def main():
             opt = torch.optim.Adam(params, lr=1e-3, betas=(0.9, 0.99), weight_decay=0)
             ema = ExponentialMovingAverage(model, decay=0.999)
 
+    returned = {}                              # what the last step's forward returned (--dump-outputs)
+
     def step(i):
         if args.mode == 'train':
             for p in params:
                 p.grad = None
-            bpd, logpx, _ = image_bits_per_dim_graph(model, xs[i % xs.shape[0]], arch['nvals'])
+            bpd, logpx, z = image_bits_per_dim_graph(model, xs[i % xs.shape[0]], arch['nvals'])
+            returned['logpx'], returned['z'] = logpx.detach(), z.detach()
             bpd.backward()
             if world > 1:                      # data-parallel gradient all-reduce (one flat bucket)
                 dd.allreduce_grads(params)
@@ -379,9 +412,10 @@ def main():
                 ema.apply()
             return bpd.detach()
         if image:
-            _, logpx, _ = image_logpx(model, xs[i % xs.shape[0]], arch['nvals'])
+            _, logpx, z = image_logpx(model, xs[i % xs.shape[0]], arch['nvals'])
         else:
-            _, logpx, _ = tabular_logpx(model, xs[i % xs.shape[0]])
+            _, logpx, z = tabular_logpx(model, xs[i % xs.shape[0]])
+        returned['logpx'], returned['z'] = logpx, z
         return dd.global_logpx_pair(logpx)     # the one collective per batch (its readback enqueued behind it)
 
     def loss_of(pair):
@@ -415,50 +449,14 @@ def main():
     value = world * B * args.steps / elapsed
     ms_per_step = elapsed / args.steps * 1e3
 
-    # ---- live per-kernel timing (one extra step, outside the timed region) ----
-    # The timed steps run the overlapped eval schedule (INF_OPT_EVAL_OVERLAP: x-branch series on a side stream);
-    # this step runs the sequential one, so each kernel's HIP-event duration is its own, not shared with a
-    # concurrent launch (tools/profile_round.sh runs rocprofv3 with INFLOW_EVAL_OVERLAP=0 to match).
     steps_info = [b.last_broyden['nstep'] for b in imblocks(model)]
-    overlap_prev = set_engine_option(model, _hip.INF_OPT_EVAL_OVERLAP, 0)
-    overlap_on = any(v == 1 for v in overlap_prev.values())
-    _hip.profile_begin(100000)
-    t1 = time.perf_counter()
-    run_steps(0, 1)
-    torch.cuda.synchronize()
-    prof_wall = time.perf_counter() - t1
-    stats = _hip.profile_end()
-    restore_engine_options(_hip.INF_OPT_EVAL_OVERLAP, overlap_prev)
     nps = [getattr(b, 'last_n_power_series', None) for b in imblocks(model)]
-    gemms = [s for s in stats if s['flops'] > 0]          # MFMA kernels (GEMM family + fused net)
-    dom = max(gemms, key=lambda s: s['total_ms'])
-    avg_ms = dom['total_ms'] / dom['launches']
-    achieved = dom['flops'] / dom['launches'] / (avg_ms * 1e-3) / 1e12
-    total_gemm_flops = sum(s['flops'] for s in gemms)
-    total_kernel_ms = sum(s['total_ms'] for s in stats)
-    # HBM bytes per launch of the dominant kernel from the committed rocprofv3 PMC passes (tools/pmc_summary.py:
-    # 2 FETCH_SIZE + WRITE_SIZE, MI355X_MICROARCH.md's gfx950 correction), counted only when they were measured on
-    # this kernel, batch, schedule and kernel-source build
-    traffic, traffic_src = None, None
-    pmc_path = os.path.join(REPO, 'profiles', 'pmc_dominant_kernel.json')
-    if os.path.exists(pmc_path):
-        try:
-            pmc = json.load(open(pmc_path))
-            if (pmc.get('tag') == dom['tag'] and pmc.get('batch') == B and arch_name == pmc.get('config', 'cifar10')
-                    and pmc.get('kernel_source_sha') == kernel_source_sha()):
-                traffic = pmc.get('hbm_bytes_per_launch')
-                traffic_src = 'profiles/pmc_dominant_kernel.json (%s)' % pmc.get('measured', '?')
-        except Exception:
-            traffic = None
-
-    phases = hbm_phases(stats, arch_name, B)
-
     if torch.is_tensor(bpd):
         bpd = float(bpd)
+    if args.dump_outputs and rank == 0:       # the last timed step's returns, before anything else runs
+        dump_outputs(args.dump_outputs, {'logpx': returned['logpx'], 'z': returned['z'],
+                                         ('bits_per_dim' if image else 'nats'): bpd})
     mm = mfma_mode()
-    # fp32-equivalent peak of the arithmetic the dominant kernel issues: its algorithmic FLOPs over the time its
-    # MFMA instructions take at their dense peak (engine prof peak_ms; frac = MFMA-pipe fraction)
-    peak = dom['flops'] / (dom['peak_ms'] * 1e9) if dom.get('peak_ms') else FP32_MFMA_PEAK_TFLOPS
     workload = workload_text(args, arch, B, global_batch, world)
     out = {
         'metric': METRIC[args.config] if args.mode == 'eval' else
@@ -480,39 +478,82 @@ def main():
                    'dist_backend': (torch.distributed.get_backend() if world > 1 else None),
                    'probes': args.probes, 'broyden_steps': steps_info, 'n_power_series': nps, 'mode': args.mode},
         ('bits_per_dim' if image else 'nats'): round(bpd, 6),
-        'roofline': {'bound': 'mfma', 'kernel': _hip.tag_name(dom['tag']), 'achieved': round(achieved, 2),
-                     'peak': round(peak, 1), 'unit': 'TFLOP/s', 'frac': round(achieved / peak, 4),
-                     'peak_basis': ('fp32-equivalent: algorithmic FLOPs / time of the issued MFMA instructions at '
-                                    'their dense peak (bf16/f16 %.1f TF: 6 products per fp32 product in bf16x6 phases, '
-                                    '3 in f16x3 phases; f32 %.1f TF)' % (BF16_MFMA_PEAK_TFLOPS, FP32_MFMA_PEAK_TFLOPS)),
-                     'flops_basis': 'algorithmic fp32 FLOPs of the net (2 per multiply-add), not MFMA instruction FLOPs',
-                     'traffic': traffic, 'avg_launch_ms': round(avg_ms, 4), 'launches_per_step': dom['launches'],
-                     'traffic_source': traffic_src, 'phases': phases,
-                     'algorithmic_bytes_per_launch': dom['bytes'] / dom['launches'],
-                     'schedule': ('per-kernel durations from one extra step on the sequential eval schedule (timed '
-                                  'steps: %s)' % ('x-branch series on a side stream' if overlap_on else 'sequential'))
-                     if image else 'per-kernel durations from one extra step (one stream: the x-branch log-det and '
-                                   'x_embed are one launch)',
-                     'flops_per_launch': dom['flops'] / dom['launches']},
-        'path': {'gemm_tflops_per_step': round(total_gemm_flops / 1e12, 4),
-                 'gemm_flop_rate_tflops': round(total_gemm_flops / (prof_wall * 1e12), 2),
-                 'kernel_busy_frac': round(total_kernel_ms / (prof_wall * 1e3), 3),
-                 'kernel_busy_basis': ('sum of kernel times / wall time of the extra sequential-schedule profiling '
-                                       'step; the timed (overlapped) steps: rocprofv3 kernel trace, '
-                                       'profiles/r04/timeline_timed_window.json'),
-                 'kernels': sorted([{'kernel': _hip.tag_name(s['tag']), 'launches': s['launches'],
-                                     'ms': round(s['total_ms'], 3),
-                                     'tflops': round(s['flops'] / (s['total_ms'] * 1e9), 2) if s['flops'] else None,
-                                     'gbs': round(s['bytes'] / (s['total_ms'] * 1e6), 1)}
-                                    for s in stats], key=lambda r: -r['ms'])[:12]},
         'cpu_baseline': None,
     }
-    if rank == 0 and world == 1 and args.cpu_baseline and arch_name != 'celebahq256' and args.mode != 'train':
-        cb, delta, ref_bpd = cpu_baseline(arch, sd, model, device, args.cpu_batch if image else B, args.cpu_reps,
-                                          training=args.mode == 'trainfwd')
-        out['cpu_baseline'] = cb
-        out['bpd_delta_vs_oracle' if image else 'nats_delta_vs_oracle'] = delta
-        out['speedup_vs_cpu_baseline'] = round(value / cb['value'], 1)
+    if args.full:
+        # ---- live per-kernel timing (one extra step, outside the timed region) ----
+        # The timed steps run the overlapped eval schedule (INF_OPT_EVAL_OVERLAP: x-branch series on a side stream);
+        # this step runs the sequential one, so each kernel's HIP-event duration is its own, not shared with a
+        # concurrent launch (tools/profile_round.sh runs rocprofv3 with INFLOW_EVAL_OVERLAP=0 to match).
+        overlap_prev = set_engine_option(model, _hip.INF_OPT_EVAL_OVERLAP, 0)
+        overlap_on = any(v == 1 for v in overlap_prev.values())
+        _hip.profile_begin(100000)
+        t1 = time.perf_counter()
+        run_steps(0, 1)
+        torch.cuda.synchronize()
+        prof_wall = time.perf_counter() - t1
+        stats = _hip.profile_end()
+        restore_engine_options(_hip.INF_OPT_EVAL_OVERLAP, overlap_prev)
+        nps = [getattr(b, 'last_n_power_series', None) for b in imblocks(model)]
+        gemms = [s for s in stats if s['flops'] > 0]          # MFMA kernels (GEMM family + fused net)
+        dom = max(gemms, key=lambda s: s['total_ms'])
+        avg_ms = dom['total_ms'] / dom['launches']
+        achieved = dom['flops'] / dom['launches'] / (avg_ms * 1e-3) / 1e12
+        total_gemm_flops = sum(s['flops'] for s in gemms)
+        total_kernel_ms = sum(s['total_ms'] for s in stats)
+        # HBM bytes per launch of the dominant kernel from the committed rocprofv3 PMC passes (tools/pmc_summary.py:
+        # 2 FETCH_SIZE + WRITE_SIZE, MI355X_MICROARCH.md's gfx950 correction), counted only when they were measured on
+        # this kernel, batch, schedule and kernel-source build
+        traffic, traffic_src = None, None
+        pmc_path = os.path.join(REPO, 'profiles', 'pmc_dominant_kernel.json')
+        if os.path.exists(pmc_path):
+            try:
+                pmc = json.load(open(pmc_path))
+                if (pmc.get('tag') == dom['tag'] and pmc.get('batch') == B and arch_name == pmc.get('config', 'cifar10')
+                        and pmc.get('kernel_source_sha') == kernel_source_sha()):
+                    traffic = pmc.get('hbm_bytes_per_launch')
+                    traffic_src = 'profiles/pmc_dominant_kernel.json (%s)' % pmc.get('measured', '?')
+            except Exception:
+                traffic = None
+
+        phases = hbm_phases(stats, arch_name, B)
+        # fp32-equivalent peak of the arithmetic the dominant kernel issues: its algorithmic FLOPs over the time its
+        # MFMA instructions take at their dense peak (engine prof peak_ms; frac = MFMA-pipe fraction)
+        peak = dom['flops'] / (dom['peak_ms'] * 1e9) if dom.get('peak_ms') else FP32_MFMA_PEAK_TFLOPS
+        out['config']['n_power_series'] = nps
+        out['roofline'] = {
+            'bound': 'mfma', 'kernel': _hip.tag_name(dom['tag']), 'achieved': round(achieved, 2),
+            'peak': round(peak, 1), 'unit': 'TFLOP/s', 'frac': round(achieved / peak, 4),
+            'peak_basis': ('fp32-equivalent: algorithmic FLOPs / time of the issued MFMA instructions at '
+                           'their dense peak (bf16/f16 %.1f TF: 6 products per fp32 product in bf16x6 phases, '
+                           '3 in f16x3 phases; f32 %.1f TF)' % (BF16_MFMA_PEAK_TFLOPS, FP32_MFMA_PEAK_TFLOPS)),
+            'flops_basis': 'algorithmic fp32 FLOPs of the net (2 per multiply-add), not MFMA instruction FLOPs',
+            'traffic': traffic, 'avg_launch_ms': round(avg_ms, 4), 'launches_per_step': dom['launches'],
+            'traffic_source': traffic_src, 'phases': phases,
+            'algorithmic_bytes_per_launch': dom['bytes'] / dom['launches'],
+            'schedule': ('per-kernel durations from one extra step on the sequential eval schedule (timed '
+                         'steps: %s)' % ('x-branch series on a side stream' if overlap_on else 'sequential'))
+            if image else 'per-kernel durations from one extra step (one stream: the x-branch log-det and '
+                          'x_embed are one launch)',
+            'flops_per_launch': dom['flops'] / dom['launches']}
+        out['path'] = {
+            'gemm_tflops_per_step': round(total_gemm_flops / 1e12, 4),
+            'gemm_flop_rate_tflops': round(total_gemm_flops / (prof_wall * 1e12), 2),
+            'kernel_busy_frac': round(total_kernel_ms / (prof_wall * 1e3), 3),
+            'kernel_busy_basis': ('sum of kernel times / wall time of the extra sequential-schedule profiling '
+                                  'step; the timed (overlapped) steps: rocprofv3 kernel trace, '
+                                  'profiles/r04/timeline_timed_window.json'),
+            'kernels': sorted([{'kernel': _hip.tag_name(s['tag']), 'launches': s['launches'],
+                                'ms': round(s['total_ms'], 3),
+                                'tflops': round(s['flops'] / (s['total_ms'] * 1e9), 2) if s['flops'] else None,
+                                'gbs': round(s['bytes'] / (s['total_ms'] * 1e6), 1)}
+                               for s in stats], key=lambda r: -r['ms'])[:12]}
+        if rank == 0 and world == 1 and args.cpu_baseline and arch_name != 'celebahq256' and args.mode != 'train':
+            cb, delta, ref_bpd = cpu_baseline(arch, sd, model, device, args.cpu_batch if image else B, args.cpu_reps,
+                                              training=args.mode == 'trainfwd')
+            out['cpu_baseline'] = cb
+            out['bpd_delta_vs_oracle' if image else 'nats_delta_vs_oracle'] = delta
+            out['speedup_vs_cpu_baseline'] = round(value / cb['value'], 1)
     if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -1,6 +1,7 @@
 """bench.py's host logic on the CPU: the per-GPU batch of each BASELINE config (C4's global batch split over the
 ranks), the rank launcher's command (BASELINE configs[3] / VERDICT r3: `--gpus N` must start N ranks itself), and
 the pipelined per-batch readback of lib.distributed."""
+import os
 import sys
 
 import pytest
@@ -68,6 +69,36 @@ def test_roofline_phases_from_profile_stats():
     assert ph['hutchinson']['kernels'][0]['kernel'] == 'series_combine_kernel'
     assert 'pmc_phases.json[cifar10_b64]' in ph['basis']
     assert bench.hbm_phases(stats, 'cifar10', 63)['basis'].endswith('no PMC record')
+
+
+def test_plain_run_is_the_default(monkeypatch):
+    """--full (the profiling step and the CPU baseline) and --dump-outputs are off unless asked for."""
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '7', '--warmup', '2'])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--full', '--dump-outputs', 'd'])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == 'd'
+
+
+def test_dump_outputs_keeps_dtype_and_the_size_limit(tmp_path, monkeypatch):
+    """--dump-outputs: <name>.npy per array, float32 / float64 as computed; an array over its share of the limit is
+    cut to the same seeded sample of its values in every run."""
+    import numpy as np
+    arrays = {'logpx': torch.arange(6, dtype=torch.float32).view(6, 1), 'z': torch.arange(4000.).view(4, 1000),
+              'nats': 1.25}
+    bench.dump_outputs(str(tmp_path / 'a'), arrays)
+    got = {n: np.load(tmp_path / 'a' / (n + '.npy')) for n in arrays}
+    assert got['logpx'].dtype == np.float32 and got['logpx'].shape == (6, 1)
+    assert np.array_equal(got['z'], arrays['z'].numpy())
+    assert got['nats'].dtype == np.float64 and float(got['nats']) == 1.25
+    monkeypatch.setattr(bench, 'DUMP_LIMIT_BYTES', 3 * 400)           # 400 bytes per array: z is cut to 100 values
+    for d in ('b', 'c'):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    zb, zc = np.load(tmp_path / 'b' / 'z.npy'), np.load(tmp_path / 'c' / 'z.npy')
+    assert zb.shape == (100,) and np.array_equal(zb, zc) and np.all(np.diff(zb) > 0)
+    assert np.load(tmp_path / 'b' / 'logpx.npy').shape == (6, 1)
+    assert sum(os.path.getsize(tmp_path / 'b' / f) - 128 for f in os.listdir(tmp_path / 'b')) <= 3 * 400
 
 
 @pytest.mark.parametrize('config', sorted(bench.BENCH_CONFIGS))

@@ -10,7 +10,7 @@ tail -1 $O/tests.log
 for rep in 1 2; do
   for n in base cur; do
     L=; [ $n = base ] && L=gpurun_alt/lib_base.so
-    INFLOW_LIB=$L timeout -k 10 240 python bench.py --config celebahq256 --batch 4 --cpu-baseline 0 --steps 4 --warmup 1 > $O/c5_${n}_$rep.json 2>/dev/null
+    INFLOW_LIB=$L timeout -k 10 240 python bench.py --full --config celebahq256 --batch 4 --cpu-baseline 0 --steps 4 --warmup 1 > $O/c5_${n}_$rep.json 2>/dev/null
     python -c "import json
 d=json.loads(open('$O/c5_${n}_$rep.json').read().strip().splitlines()[-1]); print('$n', d['value'], d['ms_per_step'], [(k['kernel'], k['launches'], round(k['ms'],3)) for k in d['path']['kernels'][:4]])"
   done

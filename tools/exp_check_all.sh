@@ -12,8 +12,8 @@ for rep in 1 2; do
   for n in base cur; do
     L=; [ $n = base ] && L=gpurun_alt/lib_base.so
     [ $n = base ] && [ ! -f gpurun_alt/lib_base.so ] && continue
-    INFLOW_LIB=$L timeout -k 10 240 python bench.py --cpu-baseline 0 --steps 20 --warmup 5 > $O/b64_${n}_$rep.json 2>/dev/null
-    INFLOW_LIB=$L timeout -k 10 200 python bench.py --config power --cpu-baseline 0 --steps 10 --warmup 3 > $O/power_${n}_$rep.json 2>/dev/null
+    INFLOW_LIB=$L timeout -k 10 240 python bench.py --full --cpu-baseline 0 --steps 20 --warmup 5 > $O/b64_${n}_$rep.json 2>/dev/null
+    INFLOW_LIB=$L timeout -k 10 200 python bench.py --full --config power --cpu-baseline 0 --steps 10 --warmup 3 > $O/power_${n}_$rep.json 2>/dev/null
     python -c "import json
 for c in ('b64', 'power'):
   d=json.loads(open('$O/'+c+'_${n}_$rep.json').read().strip().splitlines()[-1]); print('$n', c, d['value'], d['ms_per_step'], d['path']['kernel_busy_frac'])"

@@ -17,7 +17,7 @@ for rep in 1 2; do
       alt) L=gpurun_alt/lib_alt.so ;;
       *) L= ;;
     esac
-    INFLOW_EVAL_OVERLAP=$EV INFLOW_LIB=$L timeout -k 10 200 python bench.py --config power --cpu-baseline 0 --steps 10 --warmup 3 > $O/${n}_$rep.json 2>/dev/null
+    INFLOW_EVAL_OVERLAP=$EV INFLOW_LIB=$L timeout -k 10 200 python bench.py --full --config power --cpu-baseline 0 --steps 10 --warmup 3 > $O/${n}_$rep.json 2>/dev/null
     python -c "import json
 d=json.loads(open('$O/${n}_$rep.json').read().strip().splitlines()[-1]); print('$n', d['value'], d['ms_per_step'], d['path']['kernel_busy_frac'], [(k['kernel'], k['launches'], round(k['ms'],3)) for k in d['path']['kernels'][:3]])"
   done
@@ -27,7 +27,7 @@ tail -1 $O/tests.log
 timeout -k 10 200 python tools/host_profile_power.py --steps 5 > $O/host_profile_power.txt 2>&1
 head -1 $O/host_profile_power.txt
 cd /tmp && export TMPDIR=/tmp
-timeout -s KILL 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 $R/bench.py --config power --cpu-baseline 0 --steps 5 --warmup 2 > $O/prof.log 2>&1
+timeout -s KILL 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 $R/bench.py --full --config power --cpu-baseline 0 --steps 5 --warmup 2 > $O/prof.log 2>&1
 F=$(find $O/prof -name '*kernel_stats.csv' | head -1)
 cp $F $O/kernel_stats_power.csv
 cp $(find $O/prof -name "*kernel_trace.csv" | head -1) $O/power_kernel_trace.csv

@@ -8,7 +8,7 @@ cd $R
 timeout -k 10 900 python -u -m pytest -x -q --timeout 300 --timeout-method thread -m gpu tests/ > $O/gpu_tests.log 2>&1 || { tail -30 $O/gpu_tests.log; exit 1; }
 tail -1 $O/gpu_tests.log
 cd /tmp && export TMPDIR=/tmp
-timeout -s KILL 200 rocprofv3 --kernel-trace --output-format csv -d $O/trace -o run -- python3 $R/bench.py --config power --cpu-baseline 0 --steps 5 --warmup 2 > $O/trace.log 2>&1
+timeout -s KILL 200 rocprofv3 --kernel-trace --output-format csv -d $O/trace -o run -- python3 $R/bench.py --full --config power --cpu-baseline 0 --steps 5 --warmup 2 > $O/trace.log 2>&1
 F=$(find $O/trace -name '*kernel_trace.csv' | head -1)
 cp $F $O/power_kernel_trace.csv
 rm -rf $O/trace

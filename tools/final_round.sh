@@ -9,5 +9,5 @@ timeout -k 10 900 python -u -m pytest -x -v --timeout 300 --timeout-method threa
 tail -1 $OUT/gpu_tests.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.txt 2>&1
 tail -2 $OUT/smoke.txt
-timeout -k 10 420 python bench.py > $OUT/bench_b64.json 2> $OUT/bench_b64.err
+timeout -k 10 420 python bench.py --full > $OUT/bench_b64.json 2> $OUT/bench_b64.err
 tail -c 300 $OUT/bench_b64.json

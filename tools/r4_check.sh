@@ -6,8 +6,8 @@ mkdir -p $OUT
 timeout -k 10 400 python -u -m pytest -x -v --timeout 200 --timeout-method thread -m gpu tests/test_gpu_parity.py \
     -k "k128 or headline or power or toy or fc" > $OUT/tests.log 2>&1 || { tail -5 $OUT/tests.log; exit 1; }
 tail -1 $OUT/tests.log
-timeout -k 10 200 python bench.py --config power --steps 5 --warmup 2 > $OUT/bench_power.json 2>/dev/null
-timeout -k 10 200 python bench.py --cpu-baseline 0 --steps 20 --warmup 3 > $OUT/bench.json 2>/dev/null
+timeout -k 10 200 python bench.py --full --config power --steps 5 --warmup 2 > $OUT/bench_power.json 2>/dev/null
+timeout -k 10 200 python bench.py --full --cpu-baseline 0 --steps 20 --warmup 3 > $OUT/bench.json 2>/dev/null
 for f in bench_power bench; do
   python - $OUT/$f.json <<'PY'
 import json, sys

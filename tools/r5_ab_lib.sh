@@ -9,7 +9,7 @@ L=implicit-normalizing-flows_amd/lib/_hip/libinflow.so
 cp $L /tmp/libinflow_base.so
 for run in base1 alt base2; do
   if [ $run = alt ]; then cp altlib/lib_$V.so $L; else cp /tmp/libinflow_base.so $L; fi
-  timeout -k 10 300 python bench.py "$@" > $O/$run.json 2>/dev/null
+  timeout -k 10 300 python bench.py --full "$@" > $O/$run.json 2>/dev/null
   python -c "import json;d=json.loads(open('$O/$run.json').read().strip().splitlines()[-1]);print('$run', d['value'], d['ms_per_step'], d['roofline']['frac'])"
 done
 cp /tmp/libinflow_base.so $L

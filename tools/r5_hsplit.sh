@@ -9,7 +9,7 @@ timeout -k 10 600 python -u -m pytest -x -q --timeout 200 --timeout-method threa
 tail -1 $O/tests.log
 for rep in 1 2; do
   for hs in 1 0; do
-    INFLOW_HSPLIT=$hs timeout -k 10 300 python bench.py --cpu-baseline 0 > $O/c10.$hs.$rep.json 2>/dev/null
+    INFLOW_HSPLIT=$hs timeout -k 10 300 python bench.py --full --cpu-baseline 0 > $O/c10.$hs.$rep.json 2>/dev/null
     python -c "import json;d=json.loads(open('$O/c10.$hs.$rep.json').read().strip().splitlines()[-1]);print('hsplit $hs', d['value'], d['ms_per_step'], d['roofline']['frac'])"
   done
 done

@@ -15,7 +15,7 @@ OFF="INFLOW_XCD=0 INFLOW_FUSED_PRESPLIT=0 INFLOW_BROYDEN_FUSED=0 INFLOW_LIB=altl
 i=0
 for cfg in "$OFF" "" "INFLOW_XCD=0" "INFLOW_FUSED_PRESPLIT=0" "INFLOW_LIB=altlib/lib_nopsa.so" "INFLOW_BROYDEN_FUSED=0" "" "$OFF"; do
   i=$((i+1))
-  env $cfg timeout -k 10 300 python bench.py --cpu-baseline 0 ${BARGS} > $O/b$i.json 2> $O/b$i.err || { echo "bench [$cfg] failed"; tail $O/b$i.err; exit 1; }
+  env $cfg timeout -k 10 300 python bench.py --full --cpu-baseline 0 ${BARGS} > $O/b$i.json 2> $O/b$i.err || { echo "bench [$cfg] failed"; tail $O/b$i.err; exit 1; }
   python - "$O/b$i.json" "$cfg" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

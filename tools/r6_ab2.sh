@@ -13,7 +13,7 @@ i=0
 L=INFLOW_LIB=altlib/lib_
 for cfg in ${CFGS:-"" "INFLOW_FUSED_PRESPLIT=0" ${L}ps_a.so ${L}ps_b.so ${L}ps_c.so ${L}ps_d2.so ${L}nosums.so ${L}nobrf.so "" "INFLOW_FUSED_PRESPLIT=0"}; do
   i=$((i+1))
-  env $cfg timeout -k 10 300 python bench.py --cpu-baseline 0 --steps 60 --warmup 5 > $O/b$i.json 2> $O/b$i.err || { echo "bench [$cfg] failed"; tail $O/b$i.err; exit 1; }
+  env $cfg timeout -k 10 300 python bench.py --full --cpu-baseline 0 --steps 60 --warmup 5 > $O/b$i.json 2> $O/b$i.err || { echo "bench [$cfg] failed"; tail $O/b$i.err; exit 1; }
   python - "$O/b$i.json" "$cfg" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -11,7 +11,7 @@ rc=$?; grep -E "passed|failed" $O/tests.log | tail -1; [ $rc -eq 0 ] || { grep -
 i=0
 for cfg in "" "INFLOW_LIB=altlib/lib_psa0.so" "INFLOW_LIB=altlib/lib_psd2.so" "" "INFLOW_LIB=altlib/lib_psa0.so" "INFLOW_LIB=altlib/lib_psd2.so"; do
   i=$((i+1))
-  env $cfg timeout -k 10 300 python bench.py --cpu-baseline 0 --steps 60 --warmup 5 > $O/b$i.json 2> $O/b$i.err || { echo "bench [$cfg] failed"; tail $O/b$i.err; exit 1; }
+  env $cfg timeout -k 10 300 python bench.py --full --cpu-baseline 0 --steps 60 --warmup 5 > $O/b$i.json 2> $O/b$i.err || { echo "bench [$cfg] failed"; tail $O/b$i.err; exit 1; }
   python - "$O/b$i.json" "$cfg" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

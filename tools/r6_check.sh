@@ -10,7 +10,7 @@ rc=$?; grep -E "passed|failed" $O/tests.log | tail -1
 timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { echo smoke failed; tail -20 $O/smoke.log; exit 1; }
 tail -1 $O/smoke.log
 for i in $(seq 1 ${NB:-2}); do
-  timeout -k 10 300 python bench.py --cpu-baseline 0 --steps 60 --warmup 5 > $O/b$i.json 2> $O/b$i.err || { echo "bench failed"; tail $O/b$i.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --cpu-baseline 0 --steps 60 --warmup 5 > $O/b$i.json 2> $O/b$i.err || { echo "bench failed"; tail $O/b$i.err; exit 1; }
   python - "$O/b$i.json" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -13,7 +13,7 @@ fi
 i=0
 for cfg in "" "INFLOW_LIB=$ALT" "" "INFLOW_LIB=$ALT"; do
   i=$((i+1))
-  env $cfg timeout -k 10 300 python bench.py --cpu-baseline 0 --steps 60 --warmup 5 > $O/b$i.json 2> $O/b$i.err || { echo "bench [$cfg] failed"; tail $O/b$i.err; exit 1; }
+  env $cfg timeout -k 10 300 python bench.py --full --cpu-baseline 0 --steps 60 --warmup 5 > $O/b$i.json 2> $O/b$i.err || { echo "bench [$cfg] failed"; tail $O/b$i.err; exit 1; }
   python - "$O/b$i.json" "$cfg" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

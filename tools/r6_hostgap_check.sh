@@ -11,7 +11,7 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -v --timeout 300 --timeout-me
 rc=$?; grep -E "passed|failed" $O/gpu_tests.log | tail -1
 [ $rc -eq 0 ] || { grep -E "FAILED|Error" $O/gpu_tests.log | head -20; exit $rc; }
 for r in 1 2; do
-  timeout -k 10 400 python bench.py --steps 60 --cpu-baseline 0 > $O/bench_cifar10_$r.json 2> $O/bench_$r.err || { tail $O/bench_$r.err; exit 1; }
+  timeout -k 10 400 python bench.py --full --steps 60 --cpu-baseline 0 > $O/bench_cifar10_$r.json 2> $O/bench_$r.err || { tail $O/bench_$r.err; exit 1; }
   python -c "import json;d=json.loads(open('$O/bench_cifar10_$r.json').read().strip().splitlines()[-1]);print(d['value'], d['ms_per_step'], d['roofline'].get('frac'))"
   # the previous commit's host Python (bench.py + lib/, same libinflow.so) on the same box
   timeout -k 10 400 python altlib/base_py/bench.py --steps 60 --cpu-baseline 0 > $O/bench_base_$r.json 2> $O/bench_base_$r.err || { tail $O/bench_base_$r.err; exit 1; }
