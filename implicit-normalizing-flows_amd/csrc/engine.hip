@@ -30,11 +30,8 @@
 // profiling brackets) skip the system-scope fence: a system-scope release writes back and invalidates the caches, so the
 // next kernel starts with a cold L2 and the CP idles ≈ 5 µs per event (kernel trace).  What the host
 // reads through these events lives in coherent pinned memory written by the kernels / copies themselves.
-#ifndef INF_EV_SYSFENCE
-#define INF_EV_SYSFENCE 0
-#endif
-constexpr unsigned INF_EV_SYNC = hipEventDisableTiming | (INF_EV_SYSFENCE ? 0u : (unsigned)hipEventDisableSystemFence);
-constexpr unsigned INF_EV_TIMING = INF_EV_SYSFENCE ? 0u : (unsigned)hipEventDisableSystemFence;
+constexpr unsigned INF_EV_SYNC = hipEventDisableTiming | hipEventDisableSystemFence;
+constexpr unsigned INF_EV_TIMING = hipEventDisableSystemFence;
 
 namespace inf {
 static thread_local int g_last_hip = 0;
@@ -683,10 +680,6 @@ static int ps_collect(Bufs& bf, int B, int T, InfBroydenStats& stats, std::vecto
 // sample against eps sqrt(d) (the reference's result for a batch of one, i.e. independent of how the batch is
 // sharded), with the decisions taken on the device (ps_decide_kernel) and stopped samples frozen.
 // stats.sample_* (host arrays, nullable) receive the per-sample outcome in that mode.
-#ifndef SAMPLE_SUMS
-#define SAMPLE_SUMS 1   // 0: conv residuals write chunk partials and a reduction launch sums them (A/B builds)
-#endif
-
 int broyden_core(InfNet* f, const ResidFn& resid, int B, int T, double eps_in, InfBroydenStats& stats,
                  std::vector<double>& lowest_ss, Bufs& bf, hipStream_t s, bool keep_f = false,
                  const StepFn* step_fn = nullptr, const StartFn* start_fn = nullptr, SpecTail* tail = nullptr,
@@ -755,7 +748,7 @@ int broyden_core(InfNet* f, const ResidFn& resid, int B, int T, double eps_in, I
   // eval_resid_part / resid_bcast, d <= 4 residual chunks per sample): the residual launch itself sums each sample
   // over its chunks (one block per sample, conv_out_resid_sample_kernel) into the slot, so no reduction launch sits
   // between it and the readback either.  (The implicit backward's residual writes chunk partials: not here.)
-  const bool zc = (f->fc || (resid_sample_sums && SAMPLE_SUMS && out_nchunk(f->d) <= 4)) && !per_sample;
+  const bool zc = (f->fc || (resid_sample_sums && out_nchunk(f->d) <= 4)) && !per_sample;
   struct PartRestore {
     Bufs& b;
     double* p;
@@ -1299,7 +1292,7 @@ int broyden_solve(InfNet* f, const float* y, int B, int T, double eps_in, InfBro
                                    B, f->d, s);
   };
   // conv nets: the one-launch start where the residual sums go straight into the readback slot (broyden_core zc)
-  const bool conv_start = !f->fc && SAMPLE_SUMS && out_nchunk(f->d) <= 4;
+  const bool conv_start = !f->fc && out_nchunk(f->d) <= 4;
   if (f->line_search) {
     // line_search(on=True) (broyden.py:66-99): the global rule only (a per-sample step size is not the reference's)
     if (f->convergence != INF_CONV_GLOBAL) return INF_ERR_UNSUPPORTED;

@@ -358,9 +358,7 @@ __global__ __launch_bounds__(H3_NT) void fcnet_h3_pair_kernel(FcPair p) {
   fcnet_h3_body<NCB, true, ACT, 0>(p.a[sel], (long)blockIdx.x - (sel ? p.nb0 : 0));
 }
 
-#ifndef FC_FWD_NCB
-#define FC_FWD_NCB 3
-#endif
+constexpr int FC_FWD_NCB = 3;   // column blocks per workgroup of the FWD kernel
 int launch_fcnet_h3(const FcArgs& a, bool jac, hipStream_t s) {
   const int S = jac ? 16 : 16 * FC_FWD_NCB;
   const unsigned nb = (unsigned)((a.B + S - 1) / S);

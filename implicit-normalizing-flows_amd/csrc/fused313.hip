@@ -30,9 +30,7 @@
 #include <map>
 #include <string>
 
-#include <type_traits>
-
-#include "kernels.h"
+#include "fused313_stage.h"
 
 namespace inf {
 
@@ -44,19 +42,7 @@ namespace inf {
 //                    next to a 64-pixel activation tile (9C up to ~1.7K tap rows: CelebA-HQ 64x64 and
 //                    32x32 scales)
 constexpr int LDS_FULL = 40960, LDS_HALF = 20480;
-constexpr int TSLOTS = 32;
-#ifndef PB_BPIPE
-#define PB_BPIPE 1   // phase-B B operand split one K tile ahead (2-3 % per series term at s0/s1)
-#endif
-#ifndef PB_SCHED
-#define PB_SCHED 4   // with PB_BPIPE: sched_group_barrier interleave, this many VALU per MFMA
-#endif
-#ifndef PB_PRIO
-#define PB_PRIO 0    // phase-B issue priority: 1 alternate per K tile between SIMD partners, 2 younger half
-#endif
-#ifndef PB_DEPTH
-#define PB_DEPTH 2   // phase-B weight prefetch ring (K tiles); 2 = ping-pong
-#endif   // INFLOW_PHASE_STAMPS stamps per workgroup
+constexpr int TSLOTS = 32;   // INFLOW_PHASE_STAMPS stamps per workgroup
 
 __device__ __forceinline__ void load_frag8(const float* base, float* o) {
   const f32x4 v0 = *reinterpret_cast<const f32x4*>(base);
@@ -88,33 +74,11 @@ __device__ __forceinline__ f32x16 mma(const u32x4 (&a)[NP], const u32x4 (&b)[NP]
 // planes 2.70 -> 2.53 ms (kept); phase C's operand planes 2.69 (neutral alone); phase B's operand planes 3.26 (slower:
 // the per-wave split of phase B is VALU the weight-stream-bound loop hides under its MFMAs, and the planes cost a put
 // and a barrier), so phase B keeps the per-wave split
-#ifndef PS_A
-#define PS_A 1
-#endif
-#ifndef PS_B
-#define PS_B 0
-#endif
-#ifndef PS_C
-#define PS_C 1
-#endif
-// Wide kernel build options measured and not kept (round 6, one box, s2 VJP ms per step 2.56 / 2.52 with both vs 2.54 /
-// 2.45 without; stamps: staging 18.9 k and phase B 22.6 k clocks, unchanged): a 4-deep phase-B weight ring for the
-// per-wave split, and 6 halo elements per thread and pass of the series staging (the 48-channel halo in one pass)
-#ifndef WB_DEPTH
-#define WB_DEPTH 2   // wide kernel, per-wave split phase B: weight-fragment ring depth (K tiles)
-#endif
-#ifndef STAGE_WU
-#define STAGE_WU 4   // wide kernel: halo elements per thread and pass of the series staging
-#endif
-#ifndef PCD
-#define PCD 4        // pre-split wide kernel: phase C's weight-fragment ring depth for paired jobs (2: ping-pong)
-#endif
-#ifndef PSD
-#define PSD 4        // pre-split wide kernel: weight-fragment ring depth (K tiles) of phases A and B
-#endif
-#ifndef H3_AC
-#define H3_AC 1      // INF_MFMA_F16X3: phases A and C in h3 too (0: x6 there)
-#endif
+// Wide kernel, measured and not kept (round 6, one box, s2 VJP ms per step 2.56 / 2.52 with both vs 2.54 / 2.45 without;
+// stamps: staging 18.9 k and phase B 22.6 k clocks, unchanged): a 4-deep phase-B weight ring for the per-wave split,
+// and 6 halo elements per thread and pass of the series staging (the 48-channel halo in one pass)
+constexpr int PS_RING = 4;   // pre-split wide kernel: weight-fragment ring depth (K tiles) of phase A and of phase C's
+                             // paired jobs
 
 // fragment-major offset of (row block rb, k tile kt) for a matrix with nkt K tiles
 __device__ __forceinline__ long frag_off(int rb, int kt, int nkt, int lane) {
@@ -127,7 +91,7 @@ template <int TM, int MODE, int F_BN, int F_LDS_FLOATS, int SPL = 0, int NW = 8>
 __device__ __forceinline__ void net313_body(const Net313Pair& pr) {
   constexpr int NT = 64 * NW;                        // threads per workgroup
   constexpr bool H3 = SPL == 2;
-  constexpr bool H3AC = H3 && H3_AC;                  // phases A and C in h3 as well
+  constexpr bool H3AC = H3;                           // INF_MFMA_F16X3: phases A and C in h3 as well
   constexpr int NPAC = H3AC ? 2 : 3;                  // weight / operand planes of phases A and C
   constexpr int HID = NW * 32 * TM;
   constexpr int NB = F_BN / 32;                     // 32-pixel column tiles per wave
@@ -161,25 +125,23 @@ __device__ __forceinline__ void net313_body(const Net313Pair& pr) {
   // tile geometry: `rows` image rows of `seg` pixels (seg = min(W, 64))
   const int seg = a.seg, rows = F_BN / seg;
   const int y0 = p0 / a.W, x0 = p0 - y0 * a.W;
-  const int RH = rows + 2, CW = seg + 2;
-  const int vhn = a.C * RH * CW;
-  // K-padding rows of the im2col point at vh[vhn]; phase A reads vh[koff + pix], so the zero run
-  // after the halo must cover every pixel offset of the tile: rows * CW floats.
-  const int vhz = vhn + rows * CW;
+  const HaloGeom hg{a.C, a.H, a.W, seg, rows, a.K1pad, img, tile, y0, x0};
+  const int CW = hg.CW(), vhz = hg.vhz();
   float* t = smem;                                  // [HID][F_BN] activation tile
   int* koff = reinterpret_cast<int*>(smem + HID * F_BN);   // [K1pad] im2col offsets into vh
   float* vh = smem + HID * F_BN + a.K1pad;          // [C][RH][CW] halo tile + rows*CW zeros
-  // Pre-split B operands (the wide 32-pixel variant in h3, INF_OPT_FUSED_PRESPLIT): every phase's B operand is split
-  // into its fp16 (h, l) planes once, by the threads that produce it, in the MFMA B-fragment order
-  // [(K tile * NB + column block) * 2 + plane][64 lanes] x 16 B, instead of by each of the 8 waves that consume it.
-  // Phase A's im2col planes sit below the column maxima (when they fit); phases B and C's in the activation tile's
-  // space (the same 4 bytes per element as the fp32 tile).  Same scales, same rounding: bitwise the same results.
+  // Pre-split B operands (the wide 32-pixel variant in h3, INF_OPT_FUSED_PRESPLIT): the B operands of phases A and C
+  // are split into their fp16 (h, l) planes once, by the threads that produce them, in the MFMA B-fragment order
+  // [(K tile * NB + column block) * 2 + plane][64 lanes] x 16 B, instead of by each of the 8 waves that consume them
+  // (phase B keeps the per-wave split, see above).  Phase A's im2col planes sit below the column maxima (when they
+  // fit); phase C's in the activation tile's space (the same 4 bytes per element as the fp32 tile).  Same scales, same
+  // rounding: bitwise the same results.
   constexpr bool PS = H3AC && F_LDS_FLOATS == LDS_FULL && F_BN == 32 && NW == 8;
   const bool ps = PS && !(pr.dbg & 32);
   const int psa_floats = a.K1pad * 32 * NB;
   u32x4* const pa = reinterpret_cast<u32x4*>(smem + F_LDS_FLOATS - 32 - NW * F_BN - psa_floats);
-  const bool psb = PS_B && ps, psc = PS_C && ps;    // (per-phase build switches: bisecting A/B builds)
-  const bool psa = PS_A && ps && HID * F_BN + a.K1pad + vhz <= F_LDS_FLOATS - 32 - NW * F_BN - psa_floats;
+  const bool psc = ps;
+  const bool psa = ps && HID * F_BN + a.K1pad + vhz <= F_LDS_FLOATS - 32 - NW * F_BN - psa_floats;
   u32x4* const tpl = reinterpret_cast<u32x4*>(t);
   // this lane's four values of accumulator group g (rows 8 g + 4 lh + q of row block rb, column block b) into the
   // planes: K tile 2 rb + (g >> 1), consumer lane 32 (g & 1) + li, k-slots 4 lh + q (one ds_write_b64 per plane)
@@ -212,145 +174,29 @@ __device__ __forceinline__ void net313_body(const Net313Pair& pr) {
 #pragma unroll
     for (int m = 0; m < TM; ++m) ldw<NPAC>(A1w, (long)(rbw0 + m) * nkt1, lane, pa0[m]);
   }
-  float hmx = 0.f;                                  // H3AC: this thread's max |staged halo value|
-  // ---- stage the input halo tile (zero padded; forward applies the preact swish) ----
-  // Series chaining: the input is the previous VJP's packed taps; the tap sum, the preact swish'
-  // multiplier and that term's trace partial (conv_out's OM_VJP work) happen here instead.
-  const float* in = a.in + (long)img * a.C * P;
-  const float pre_sp = a.pre_beta ? softplus_f(ldc(a.pre_beta)) : 0.f;
+  // ---- stage the input halo tile (fused313_stage.h; the forward applies the preact swish, the series chains) ----
+  float hmx = 0.f;                                  // this thread's max |staged halo value| (H3AC; dead otherwise)
   double dacc = 0.0;
-  if (a.in_taps) {
-    const float* ytap = a.in_taps + (long)img * a.M3 * P;
-    const float* mx = a.vmul_x ? a.vmul_x + (long)img * a.C * P : nullptr;
-    const float* ep = a.dot_eps ? a.dot_eps + (long)img * a.C * P : nullptr;
-    const float msp = a.vmul_x ? softplus_f(ldc(a.vmul_beta)) : 0.f;
-    // Up to 4 halo elements per pass with unconditional (clamped-address) loads, all issued before any
-    // is used: 44 loads in flight per thread instead of one bounds-checked chain per element.  The pass
-    // width NU is wave-uniform and a compile-time constant per branch (a runtime slot guard lets the
-    // compiler fuse each slot's loads with their use), so a small halo costs one pass of 11 loads.
-    const float* mxp = mx ? mx : ytap;
-    const float* epp = ep ? ep : ytap;
-    float* accw = a.acc_w ? a.acc_w + (long)img * a.C * P : nullptr;   // Neumann-vector accumulator
-    const float* awp = accw ? accw : ytap;
-    auto pass = [&](auto nuc, int i0) {
-      constexpr int NU = decltype(nuc)::value;
-      float tv[NU][9], xm[NU], ev[NU], wv[NU];
-#pragma unroll
-      for (int u = 0; u < NU; ++u) {
-        const int i = i0 + u * NT;
-        const int ic = i < vhn ? i : 0;
-        const int c = ic / (RH * CW), rr = ic - c * RH * CW;
-        const int hy = rr / CW, hx = rr - hy * CW;
-        const int yq = min(max(y0 + hy - 1, 0), a.H - 1), xq = min(max(x0 + hx - 1, 0), a.W - 1);
-        const long ee = (long)c * P + yq * a.W + xq;
-        const float* yc = ytap + (long)c * 9 * P;
-#pragma unroll
-        for (int tp = 0; tp < 9; ++tp) {
-          const int y2 = min(max(yq + tp / 3 - 1, 0), a.H - 1), x2 = min(max(xq + tp % 3 - 1, 0), a.W - 1);
-          tv[u][tp] = yc[(long)tp * P + y2 * a.W + x2];
-        }
-        xm[u] = mxp[ee];
-        ev[u] = epp[ee];
-        wv[u] = awp[ee];
-      }
-#pragma unroll
-      for (int u = 0; u < NU; ++u) {
-        const int i = i0 + u * NT;
-        const int ic = i < vhn ? i : 0;
-        const int rr = ic % (RH * CW);
-        const int hy = rr / CW, hx = rr - hy * CW;
-        const int yy = y0 + hy - 1, xx = x0 + hx - 1;
-        const bool in_img = i < vhn && yy >= 0 && yy < a.H && xx >= 0 && xx < a.W;
-        const int ok = in_img ? ((hy >= 1 && hy <= rows && hx >= 1 && hx <= seg) ? 2 : 1) : 0;
-        float v = 0.f;
-#pragma unroll
-        for (int tp = 0; tp < 9; ++tp) {
-          const int y2 = yy + tp / 3 - 1, x2 = xx + tp % 3 - 1;
-          const bool vt = y2 >= 0 && y2 < a.H && x2 >= 0 && x2 < a.W;
-          v += vt ? tv[u][tp] : 0.f;
-        }
-        if (mx) v = v * swish_fast_d(xm[u], msp);
-        v = ok ? v : 0.f;
-        if (ep && ok == 2) dacc += (double)v * (double)ev[u];
-        if (accw && ok == 2) accw[(long)(ic / (RH * CW)) * P + yy * a.W + xx] = fmaf(a.acc_coef, v, wv[u]);
-        if constexpr (H3AC) hmx = fmaxf(hmx, fabsf(v));
-        if (i < vhz) vh[i] = v;
-      }
-    };
-    // (the wide variant has the registers for 6 units, 66 loads in flight: the 8x8 scale's 48-channel halo in one pass
-    // instead of two round trips)
-    constexpr int SU = (F_BN == 32 && F_LDS_FLOATS == LDS_FULL) ? STAGE_WU : 4;
-    for (int i0 = tid; i0 < vhz; i0 += NT * SU) {
-      const int nu = min(SU, (vhz - (i0 - tid) + NT - 1) / NT);     // wave-uniform
-      if (SU >= 6 && nu >= 6) pass(std::integral_constant<int, (SU >= 6 ? 6 : 4)>(), i0);
-      else if (SU >= 5 && nu == 5) pass(std::integral_constant<int, (SU >= 5 ? 5 : 4)>(), i0);
-      else if (nu >= 4) pass(std::integral_constant<int, 4>(), i0);
-      else if (nu == 3) pass(std::integral_constant<int, 3>(), i0);
-      else if (nu == 2) pass(std::integral_constant<int, 2>(), i0);
-      else pass(std::integral_constant<int, 1>(), i0);
-    }
-  } else {
-    // FU elements per thread and pass, every load from a clamped address issued before any is used (a bounds-checked
-    // load per element waited for memory once per element: 6 round trips per thread at the 8x8 scale's 48 channels)
-    constexpr int FU = 8;
-    for (int i0 = tid; i0 < vhz; i0 += NT * FU) {
-      float lv[FU];
-      bool ok[FU];
-#pragma unroll
-      for (int u = 0; u < FU; ++u) {
-        const int i = i0 + u * NT;
-        const int ic = i < vhn ? i : 0;
-        const int c = ic / (RH * CW), rr = ic - c * RH * CW;
-        const int hy = rr / CW, hx = rr - hy * CW;
-        const int yy = y0 + hy - 1, xx = x0 + hx - 1;
-        ok[u] = i < vhn && yy >= 0 && yy < a.H && xx >= 0 && xx < a.W;
-        lv[u] = in[(long)c * P + min(max(yy, 0), a.H - 1) * a.W + min(max(xx, 0), a.W - 1)];
-      }
-#pragma unroll
-      for (int u = 0; u < FU; ++u) {
-        const int i = i0 + u * NT;
-        float v = 0.f;
-        if (ok[u]) {
-          v = lv[u];
-          if (a.pre_beta) v = swish_fast_f(v, pre_sp);
-        }
-        if constexpr (H3AC) hmx = fmaxf(hmx, fabsf(v));
-        if (i < vhz) vh[i] = v;
-      }
-    }
-  }
+  stage_halo<NT, 8, true>(a, hg, tid, vh, hmx, dacc, [](bool) {});
   // per-tile trace partial: wave sums -> a reserved LDS slot at the end of the LDS (never reused)
   double* red = reinterpret_cast<double*>(smem + F_LDS_FLOATS - 16);
   // H3: per-wave column maxima of the phase-B / phase-C operand [NW][F_BN] and the halo maxima [NW] of
   // phase A, just below the trace-partial slots
   float* cmax = smem + F_LDS_FLOATS - 16 - 16 - NW * F_BN;
   float* hmax = smem + F_LDS_FLOATS - 32;
-  if constexpr (H3AC) {
-    const float w = wave_max(hmx);
-    if (lane == 0) hmax[wid] = w;
-  }
-  if (a.dot_part) {
-    const double w = wave_sum(dacc);
-    if (lane == 0) red[wid] = w;
-  }
-  for (int k = tid; k < a.K1pad; k += NT) {
-    int o = vhn;                                    // zero slot for the K padding
-    if (k < 9 * a.C) {
-      const int c = k / 9, tt = k - c * 9;
-      o = c * RH * CW + (tt / 3) * CW + (tt % 3);
-    }
-    koff[k] = o;
-  }
-  // pixel offsets of this lane's two columns inside the halo tile, and in the image
-  int pix[NB], gp[NB];
+  if constexpr (H3AC) put_wave_max(lane, wid, hmx, hmax);
+  put_wave_dot(a, lane, wid, dacc, red);
+  fill_koff<NT>(hg, tid, koff);
+  // halo-tile offsets of this lane's pixel in each column block
+  int pix[NB];
 #pragma unroll
   for (int b = 0; b < NB; ++b) {
     const int n = b * 32 + li;
-    const int py = n / seg, px = n - py * seg;
-    pix[b] = py * CW + px;
-    gp[b] = (y0 + py) * a.W + x0 + px;
+    const int py = n / seg;
+    pix[b] = py * CW + (n - py * seg);
   }
-  // gp for a runtime column index (phase C tasks): arithmetic, not gp[b] (which would live in scratch)
+  // image offset of this lane's pixel in column block b (phase C tasks: b is a runtime index, so arithmetic
+  // rather than a per-block array, which would live in scratch)
   auto gp_rt = [&](int b) {
     const int n = b * 32 + li;
     const int py = n / seg;
@@ -394,12 +240,7 @@ __device__ __forceinline__ void net313_body(const Net313Pair& pr) {
   }
   __syncthreads();
   STAMP(1);
-  if (a.dot_part && tid == 0) {
-    double s = 0.0;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) s += red[w];
-    a.dot_part[(long)img * a.dot_nchunk + tile] = s;
-  }
+  write_dot_part<NW>(a, hg, tid, red);
 
   f32x16 acc[TM][NB];
   auto zero_acc = [&]() {
@@ -420,14 +261,7 @@ __device__ __forceinline__ void net313_body(const Net313Pair& pr) {
     // H3AC: one scale for the tile's halo (its max over all waves), unscaled after the K loop
     float sA = 1.f;
     int eA = 0;
-    if constexpr (H3AC) {
-      float m_ = 0.f;
-#pragma unroll
-      for (int w = 0; w < NW; ++w) m_ = fmaxf(m_, hmax[w]);
-      const int sc = h3_scale_exp(m_);
-      sA = __builtin_amdgcn_ldexpf(1.f, sc);
-      eA = -(sc + ldc(a.Ah_exp));
-    }
+    if constexpr (H3AC) phaseA_scale<NW>(a, hmax, sA, eA);
     auto ld3 = [&](int m, int kt, u32x4 (&o)[NPAC]) { ldw<NPAC>(A1w, (long)(rbw + m) * nkt + kt, lane, o); };
     auto gather_path = [&]() {
       // B operand (im2col gather from the halo tile) one K tile ahead: its LDS reads and split overlap
@@ -522,8 +356,8 @@ __device__ __forceinline__ void net313_body(const Net313Pair& pr) {
 #pragma unroll
             for (int b = 0; b < NB; ++b) acc[m][b] = mfma_h3(af[m], o[b][0], o[b][1], acc[m][b]);
         };
-        // weight fragments in a ring PSD K tiles deep (the tail reloads the last tile: straight-line steps)
-        u32x4 wr[PSD][TM][NPAC];
+        // weight fragments in a ring PS_RING K tiles deep (the tail reloads the last tile: straight-line steps)
+        u32x4 wr[PS_RING][TM][NPAC];
 #pragma unroll
         for (int m = 0; m < TM; ++m) {
           if constexpr (PRE_A) {
@@ -534,14 +368,14 @@ __device__ __forceinline__ void net313_body(const Net313Pair& pr) {
           }
         }
 #pragma unroll
-        for (int d = 1; d + 1 < PSD; ++d)
+        for (int d = 1; d + 1 < PS_RING; ++d)
 #pragma unroll
           for (int m = 0; m < TM; ++m) ld3(m, min(d, nkt - 1), wr[d][m]);
-        for (int kt = 0; kt < nkt; kt += PSD) {
+        for (int kt = 0; kt < nkt; kt += PS_RING) {
 #pragma unroll
-          for (int d = 0; d < PSD; ++d) {
+          for (int d = 0; d < PS_RING; ++d) {
 #pragma unroll
-            for (int m = 0; m < TM; ++m) ld3(m, min(kt + d + PSD - 1, nkt - 1), wr[(d + PSD - 1) % PSD][m]);
+            for (int m = 0; m < TM; ++m) ld3(m, min(kt + d + PS_RING - 1, nkt - 1), wr[(d + PS_RING - 1) % PS_RING][m]);
             if (kt + d < nkt) tileP(kt + d, wr[d]);
           }
         }
@@ -620,8 +454,7 @@ __device__ __forceinline__ void net313_body(const Net313Pair& pr) {
             if constexpr (MODE == MODE_SAVE || MODE == MODE_EVALSAVE) dv[r] = swish_fast_d(z, sp1);
           }
           if constexpr (H3) cm[b] = fmaxf(cm[b], fabsf(v));
-          if (psb) acc[m][b][r] = v;                  // (pre-split: put below, at the column scales)
-          else t[o * F_BN + b * 32 + li] = v;
+          t[o * F_BN + b * 32 + li] = v;
         }
         if constexpr (MODE == MODE_SAVE || MODE == MODE_EVALSAVE) store_d(a.d1, m, b, dv);
       }
@@ -653,13 +486,6 @@ __device__ __forceinline__ void net313_body(const Net313Pair& pr) {
       hs[b] = __builtin_amdgcn_ldexpf(1.f, sc);
       hexp[b] = -(sc + sw);
     }
-    if (psb) {
-#pragma unroll
-      for (int m = 0; m < TM; ++m)
-#pragma unroll
-        for (int b = 0; b < NB; ++b) put_planes(tpl, rbw + m, b, acc[m][b], hs[b]);
-      __syncthreads();
-    }
     zero_acc();
     auto ld2 = [&](int m, int kt, u32x4 (&o)[2]) {
       const u32x4* q = A2h + ((long)((rbw + m) * nkt + kt) * 2) * 64 + lane;
@@ -683,40 +509,11 @@ __device__ __forceinline__ void net313_body(const Net313Pair& pr) {
 #pragma unroll
         for (int b = 0; b < NB; ++b) acc[m][b] = mfma_h3(af[m], o.h[b], o.l[b], acc[m][b]);
     };
-    if (psb) {
-      // B operand from the planes; the weight fragments in a ring PSD K tiles deep (32 registers of
-      // accumulators leave the room)
-      u32x4 wr[PSD][TM][2], hb[NB], lb[NB];
-#pragma unroll
-      for (int d = 0; d + 1 < PSD; ++d)
-#pragma unroll
-        for (int m = 0; m < TM; ++m) ld2(m, d, wr[d][m]);
-#pragma unroll
-      for (int b = 0; b < NB; ++b) {
-        hb[b] = tpl[(b * 2) * 64 + lane];
-        lb[b] = tpl[(b * 2 + 1) * 64 + lane];
-      }
-      static_assert(nkt % PSD == 0, "phase-B K tiles must be a multiple of the ring depth");
-      for (int kt = 0; kt < nkt; kt += PSD) {
-#pragma unroll
-        for (int d = 0; d < PSD; ++d) {
-#pragma unroll
-          for (int m = 0; m < TM; ++m) ld2(m, min(kt + d + PSD - 1, nkt - 1), wr[(d + PSD - 1) % PSD][m]);
-          const int kn = min(kt + d + 1, nkt - 1);
-#pragma unroll
-          for (int b = 0; b < NB; ++b) {
-#pragma unroll
-            for (int m = 0; m < TM; ++m) acc[m][b] = mfma_h3(wr[d][m], hb[b], lb[b], acc[m][b]);
-            hb[b] = tpl[((kn * NB + b) * 2) * 64 + lane];
-            lb[b] = tpl[((kn * NB + b) * 2 + 1) * 64 + lane];
-          }
-        }
-      }
-    } else {
-    // weight-fragment ring: 2 K tiles (ping-pong); the wide variant (6 MFMAs per K step at NB = 1) WB_DEPTH
-    constexpr int D = (F_BN == 32 && F_LDS_FLOATS == LDS_FULL) ? WB_DEPTH : 2;
+    // weight-fragment ring: 2 K tiles (ping-pong)
+    constexpr int D = 2;
     static_assert(nkt % D == 0, "phase-B K tiles must be a multiple of the ring depth");
-    constexpr bool BPIPE = PB_BPIPE && F_LDS_FLOATS != LDS_HALF;
+    // B operand split one K tile ahead (2-3 % per series term at s0/s1; not in the 128-VGPR variant)
+    constexpr bool BPIPE = F_LDS_FLOATS != LDS_HALF;
     u32x4 ab[D][TM][2];
     BOpH bo[BPIPE ? 2 : 1];
 #pragma unroll
@@ -733,23 +530,20 @@ __device__ __forceinline__ void net313_body(const Net313Pair& pr) {
         if constexpr (BPIPE) {
           bprep(min(kt + d + 1, nkt - 1), bo[(d + 1) % 2]);
           bmma(ab[d], bo[d % 2]);
-#if PB_SCHED
           __builtin_amdgcn_sched_group_barrier(0x020, TM * 2, 0);
           __builtin_amdgcn_sched_group_barrier(0x100, 4 * NB, 0);
 #pragma unroll
           for (int i = 0; i < 3 * TM * NB - 2; ++i) {
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x002, PB_SCHED, 0);
+            __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
           }
           __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-#endif
         } else {
           bprep(kt + d, bo[0]);
           bmma(ab[d], bo[0]);
         }
       }
     }
-    }   // (per-wave split)
 #pragma unroll
     for (int m = 0; m < TM; ++m)
 #pragma unroll
@@ -784,10 +578,10 @@ __device__ __forceinline__ void net313_body(const Net313Pair& pr) {
 #pragma unroll
         for (int b = 0; b < NB; ++b) acc[m][b] = mfma_x6(af[m], o.h[b], o.m[b], o.l[b], acc[m][b]);
     };
-    // weight operand ring: PB_DEPTH K tiles of A fragments, the next D-1 in flight behind the one in use;
-    // with PB_BPIPE the B operand of the next K tile is read and split while this tile's MFMAs issue
-    constexpr int D = (F_LDS_FLOATS == LDS_HALF) ? 2 : PB_DEPTH;
-    constexpr bool BPIPE = PB_BPIPE && F_LDS_FLOATS != LDS_HALF;
+    // weight operand ring: D K tiles of A fragments (ping-pong), the next D-1 in flight behind the one in use;
+    // with BPIPE the B operand of the next K tile is read and split while this tile's MFMAs issue
+    constexpr int D = 2;
+    constexpr bool BPIPE = F_LDS_FLOATS != LDS_HALF;
     static_assert(nkt % D == 0 && D % 2 == 0, "phase-B K tiles must be a multiple of the prefetch depth");
     u32x4 ab[D][TM][3];
     BOp bo[BPIPE ? 2 : 1];
@@ -796,30 +590,14 @@ __device__ __forceinline__ void net313_body(const Net313Pair& pr) {
 #pragma unroll
       for (int m = 0; m < TM; ++m) ld3(m, d, ab[d][m]);
     if constexpr (BPIPE) bprep(0, bo[0]);
-#if PB_PRIO == 2
-    if (__builtin_amdgcn_readfirstlane(wid) >= NW / 2) __builtin_amdgcn_s_setprio(1);   // younger half wins
-#endif
     for (int kt = 0; kt < nkt; kt += D) {
 #pragma unroll
       for (int d = 0; d < D; ++d) {
         const int kn = kt + d + D - 1;
-#if PB_SCHED
-        if (true)      // (the last D-1 steps reload the last K tile: one straight-line block per step)
-#else
-        if (kn < nkt)
-#endif
-        {
+        // (the last D-1 steps reload the last K tile: one straight-line block per step)
 #pragma unroll
-          for (int m = 0; m < TM; ++m) ld3(m, min(kn, nkt - 1), ab[(d + D - 1) % D][m]);
-        }
+        for (int m = 0; m < TM; ++m) ld3(m, min(kn, nkt - 1), ab[(d + D - 1) % D][m]);
         if constexpr (BPIPE) {
-#if PB_SCHED
-#if PB_PRIO == 1
-          // the two waves of a SIMD take turns at issue priority, so neither is left alone at the end
-          // (wave id through readfirstlane: a scalar branch; a vector condition would run both setprios)
-          if (((kt + d) ^ (__builtin_amdgcn_readfirstlane(wid) >> 2)) & 1) __builtin_amdgcn_s_setprio(1);
-          else __builtin_amdgcn_s_setprio(0);
-#endif
           bprep(min(kt + d + 1, nkt - 1), bo[(d + 1) % 2]);   // (clamped: one straight-line block per step)
           bmma(ab[d], bo[d % 2]);
           // interleave: the weight loads and next tile's LDS reads first, then each MFMA followed by ~4 VALU
@@ -828,22 +606,15 @@ __device__ __forceinline__ void net313_body(const Net313Pair& pr) {
 #pragma unroll
           for (int i = 0; i < 6 * TM * NB - 2; ++i) {
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x002, PB_SCHED, 0);
+            __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
           }
           __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-#else
-          if (kt + d + 1 < nkt) bprep(kt + d + 1, bo[(d + 1) % 2]);
-          bmma(ab[d], bo[d % 2]);
-#endif
         } else {
           bprep(kt + d, bo[0]);
           bmma(ab[d], bo[0]);
         }
       }
     }
-#if PB_PRIO
-    __builtin_amdgcn_s_setprio(0);
-#endif
   } else {
     zero_acc();
     constexpr int nkt = HID / 16;
@@ -1113,17 +884,17 @@ __device__ __forceinline__ void net313_body(const Net313Pair& pr) {
 #pragma unroll
             for (int g = 0; g < G; ++g) ld3(rbj[g], kt, o[g]);
           };
-          if (PCD > 2 && psc) {
-            // B operand from the planes (no VALU in the loop): the weight fragments PCD K tiles ahead, so the loop is not
+          if (psc) {
+            // B operand from the planes (no VALU in the loop): the weight fragments PS_RING K tiles ahead, so the loop is not
             // one L2 round trip per K tile (6 MFMAs per step at G = 2)
-            static_assert(PCD <= 2 || nkt % PCD == 0, "phase-C K tiles must be a multiple of the ring depth");
-            u32x4 rg[PCD > 2 ? PCD : 1][G][NPAC];
+            static_assert(nkt % PS_RING == 0, "phase-C K tiles must be a multiple of the ring depth");
+            u32x4 rg[PS_RING][G][NPAC];
 #pragma unroll
-            for (int d = 0; d + 1 < PCD; ++d) ldg(d, rg[d]);
-            for (int kt = 0; kt < nkt; kt += PCD) {
+            for (int d = 0; d + 1 < PS_RING; ++d) ldg(d, rg[d]);
+            for (int kt = 0; kt < nkt; kt += PS_RING) {
 #pragma unroll
-              for (int d = 0; d < PCD; ++d) {
-                ldg(min(kt + d + PCD - 1, nkt - 1), rg[(d + PCD - 1) % PCD]);
+              for (int d = 0; d < PS_RING; ++d) {
+                ldg(min(kt + d + PS_RING - 1, nkt - 1), rg[(d + PS_RING - 1) % PS_RING]);
                 step(kt + d, rg[d]);
               }
             }
@@ -1232,12 +1003,8 @@ __global__ __launch_bounds__(512) void net313_kernel_w(Net313Pair pr) {
 enum { V64 = 0, VHALF = 1, VWIDE = 2 };
 
 static int tile_fits(int hid, int C, int H, int W, int bn, int ldsf) {
-  const int P = H * W;
-  const int seg = W < bn ? W : bn;
-  if (P % bn != 0 || bn % seg != 0 || (W > bn && W % bn != 0)) return 0;
-  const int rows = bn / seg;
-  const long k1pad = (9L * C + 15) / 16 * 16;
-  const long need = (long)hid * bn + k1pad + (long)C * (rows + 2) * (seg + 2) + (long)rows * (seg + 2);
+  if (!halo_tiles(H, W, bn)) return 0;
+  const long need = (long)hid * bn + halo_lds_floats(C, W, bn);
   return need <= ldsf - 32 - 8 * bn;       // last 16 floats: trace-partial slots; 16 + 8 x bn: H3 halo / column maxima
 }
 static int variant_fits(int hid, int C, int H, int W, int v) {
@@ -1327,12 +1094,9 @@ static void timing_collect(const char* key, long nwg, hipStream_t s) {
   }
 }
 
-// XCD_PAIRS=1 builds place the two nets of a pair launch on different XCDs (Net313Pair::xcd).  Measured and not kept as
-// the default (round 6): the per-launch kernel times did not move (k128 VJP 15.74 vs 15.76 ms per step,
-// s2 VJP 3.21 vs 3.16), so each XCD's L2 already serves both nets' weight planes
-#ifndef XCD_PAIRS
-#define XCD_PAIRS 0
-#endif
+// Measured and not kept (round 6): the two nets of a pair launch placed on different XCDs.  The per-launch
+// kernel times did not move (k128 VJP 15.74 vs 15.76 ms per step, s2 VJP 3.21 vs 3.16), so each XCD's L2 already serves
+// both nets' weight planes
 
 int launch_net313_multi(const Net313Args* args, int nnets, int hid, int mode, hipStream_t s, int layout_nets) {
   if (layout_nets <= 0) layout_nets = nnets;
@@ -1357,10 +1121,10 @@ int launch_net313_multi(const Net313Args* args, int nnets, int hid, int mode, hi
   // VJP / EVAL variant policy (per net, INF_OPT_FUSED_K128): 0 the 64-pixel kernel only, 1 the 128-pixel
   // K-chunked kernel where its grid still covers every CU (default), 2 wherever it fits (tests)
   const int k128_pol = a0.k128;
-  const bool k128 = k128_pol && H3_AC && h3_args && var == V64 && net313k_fits(hid, a0.C, a0.H, a0.W) &&
+  const bool k128 = k128_pol && h3_args && var == V64 && net313k_fits(hid, a0.C, a0.H, a0.W) &&
                     (k128_pol == 2 || (long)nnets * a0.B * (P / 128) >= 256);
   // the two-per-CU 64-pixel VJP (fused313p.hip): INF_OPT_FUSED_K128 = 3, VJP launches
-  const bool p64 = mode == MODE_VJP && k128_pol == 3 && H3_AC && h3_args && var == V64 &&
+  const bool p64 = mode == MODE_VJP && k128_pol == 3 && h3_args && var == V64 &&
                    net313p_fits(hid, a0.C, a0.H, a0.W);
   const int tbn = p64 ? 64 : (k128 ? 128 : bn);
   for (int i = 0; i < 2; ++i) pr.a[i].seg = a0.W < tbn ? a0.W : tbn;
@@ -1368,7 +1132,6 @@ int launch_net313_multi(const Net313Args* args, int nnets, int hid, int mode, hi
   pr.max_ksplit = 8;
   pr.dbg = (a0.exact_scale ? 16 : 0) | (a0.presplit ? 0 : 32);        // INF_OPT_K128_EXACT_SCALE: chunk 1's exact-scale path on every tile
   pr.reverse = a0.tile_order;
-  pr.xcd = XCD_PAIRS && nnets == 2 && (pr.nb0 * 2) % 8 == 0;
   pr.tbuf = nullptr;
   if (INFLOW_PHASE_STAMPS) pr.tbuf = timing_buf(pr.nb0 * nnets);   // tools/build_alt_k128.py "stamps" builds only
   const unsigned nb = (unsigned)(pr.nb0 * nnets);
@@ -1440,7 +1203,7 @@ int launch_net313_multi(const Net313Args* args, int nnets, int hid, int mode, hi
     // (EVALSAVE: x + d1/d2 writes + taps, the same expression)
     // MFMA instruction FLOPs: exact fp32 1 per algorithmic FLOP (f32 peak), x6 6 (bf16), h3 phase B 3 (f16)
     const double pk = !split ? npx * (fA + fB + fC) / PEAK_F32_FLOPS_PER_MS
-                             : npx * ((h3 && H3_AC ? 3.0 : 6.0) * (fA + fC) + (h3 ? 3.0 : 6.0) * fB) / PEAK_BF16_FLOPS_PER_MS;
+                             : npx * ((h3 ? 3.0 : 6.0) * (fA + fC) + (h3 ? 3.0 : 6.0) * fB) / PEAK_BF16_FLOPS_PER_MS;
     prof_end_launch(s, 500 + 10 * var + mode, npx * (fA + fB + fC), bytes, pk);   // 50x / 51x (_h) / 52x (_w)
   }
   return INF_OK;

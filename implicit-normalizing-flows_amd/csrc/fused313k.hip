@@ -35,9 +35,7 @@
 //
 // The geometry (C, W) of the CIFAR-10 and CelebA-HQ 256 scales is a template parameter (CT, WT; 0 = from the
 // arguments), so the halo index arithmetic, phase A's K loop and phase C's row-block loop are compile-time.
-#include <type_traits>
-
-#include "kernels.h"
+#include "fused313_stage.h"
 
 namespace inf {
 
@@ -50,47 +48,14 @@ constexpr int KB_HID = 512;
 constexpr int KB_LDS = 40960;       // floats (160 KiB)
 constexpr int KB_CHUNK = 32768;     // floats: 16 K tiles x 4 column blocks x 2 planes x 64 lanes x 16 B
 constexpr int KB_TSLOTS = 32;
-#ifndef K128_D2EARLY
-#define K128_D2EARLY 0              // 1: chunk 1's first d2 loads issued in phase B's last K step instead of after phase B;
-#endif                              // measured neutral (16.83 / 16.89 vs 16.81 / 16.75 ms per step, same box; 9 spills)
-#ifndef K128_PSA0
-#define K128_PSA0 1                 // chunk 0's im2col planes in the chunk buffer where they do not fit beside the halo
-#endif
-#ifndef K128_PSA
-#define K128_PSA 1                  // phase A's im2col planes split once per workgroup (0: per wave, A/B builds)
-#endif
-
-// the two (h, l) planes of fragment tile `tile` (fragment-major, launch_split2h order)
-__device__ __forceinline__ void ldw2(const u32x4* base, long tile, int lane, u32x4 (&o)[2]) {
-  const u32x4* q = base + tile * 2 * 64 + lane;
-  o[0] = q[0];
-  o[1] = q[64];
-}
-
-// 4 consecutive fp32 values (rows q = 0..3 of one accumulator group) -> scaled fp16 h / l pieces, packed
-__device__ __forceinline__ void split4h(float v0, float v1, float v2, float v3, float S, uint2& h, uint2& l) {
-  const _Float16 h0 = (_Float16)(v0 * S), h1 = (_Float16)(v1 * S), h2 = (_Float16)(v2 * S), h3 = (_Float16)(v3 * S);
-  const _Float16 l0 = (_Float16)__builtin_fmaf(v0, S, -(float)h0), l1 = (_Float16)__builtin_fmaf(v1, S, -(float)h1);
-  const _Float16 l2 = (_Float16)__builtin_fmaf(v2, S, -(float)h2), l3 = (_Float16)__builtin_fmaf(v3, S, -(float)h3);
-  const f16x2 a = {h0, h1}, b = {h2, h3}, c = {l0, l1}, d = {l2, l3};
-  h = make_uint2(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b));
-  l = make_uint2(__builtin_bit_cast(unsigned, c), __builtin_bit_cast(unsigned, d));
-}
-
-constexpr int kb_seg(int W) { return W < KB_BN ? W : KB_BN; }
-
 }  // namespace
 
 // 128-pixel tiles fit: whole image rows (or a 128-wide row segment), halo + im2col table + chunk buffer
 int net313k_fits(int hid, int C, int H, int W) {
   if (hid != KB_HID) return 0;
-  const int P = H * W;
-  const int seg = W < KB_BN ? W : KB_BN;
-  if (P % KB_BN != 0 || KB_BN % seg != 0 || (W > KB_BN && W % KB_BN != 0)) return 0;
+  if (!halo_tiles(H, W, KB_BN)) return 0;
   if (9 * C > 256) return 0;                      // phase A: at most 16 K tiles
-  const int rows = KB_BN / seg;
-  const long k1pad = (9L * C + 15) / 16 * 16;
-  const long need = KB_CHUNK + KB_NW * KB_BN + 8 + 2 * KB_NW + 4 + k1pad + (long)C * (rows + 2) * (seg + 2) + (long)rows * (seg + 2);
+  const long need = KB_CHUNK + KB_NW * KB_BN + 8 + 2 * KB_NW + 4 + halo_lds_floats(C, W, KB_BN);
   return need <= KB_LDS;
 }
 
@@ -130,7 +95,7 @@ __global__ __launch_bounds__(512) void net313k_kernel(Net313Pair pr) {
   // geometry: compile-time for the instantiated scales
   const int C = CT ? CT : a.C;
   const int W = WT ? WT : a.W;
-  const int seg = WT ? kb_seg(WT) : a.seg;
+  const int seg = WT ? tile_seg(WT, KB_BN) : a.seg;
   const int rows = KB_BN / seg;
   const int K1pad = CT ? (9 * CT + 15) / 16 * 16 : a.K1pad;
   const int M3 = 9 * C;
@@ -140,9 +105,8 @@ __global__ __launch_bounds__(512) void net313k_kernel(Net313Pair pr) {
   const int img = bid / tiles_per_img, tile = bid - img * tiles_per_img;
   const int p0 = tile * KB_BN;
   const int y0 = p0 / W, x0 = p0 - y0 * W;
-  const int RH = rows + 2, CW = seg + 2;
-  const int vhn = C * RH * CW;
-  const int vhz = vhn + rows * CW;                  // zero run for the K-padding rows of phase A
+  const HaloGeom hg{C, a.H, W, seg, rows, K1pad, img, tile, y0, x0};
+  const int CW = hg.CW(), vhz = hg.vhz();
   // LDS: chunk buffer | column maxima [NW][BN] | halo maxima [8] | trace partials [NW] (fp64) | flags [4] | koff | halo
   u32x4* cb = reinterpret_cast<u32x4*>(smem);
   float* cmax = smem + KB_CHUNK;
@@ -194,122 +158,15 @@ __global__ __launch_bounds__(512) void net313k_kernel(Net313Pair pr) {
   };
   if (!PRE_A0 || !a.in_taps) issue_early();         // (without preloaded weights phase A would wait for d2 anyway)
 
-  // ---- stage the input halo tile (series chaining: tap sum, preact swish', trace partial / Neumann acc) ----
+  // ---- stage the input halo tile (fused313_stage.h); the early loads go out after the last pass's loads ----
   float hmx = 0.f;
   double dacc = 0.0;
-  {
-    const float* in = a.in ? a.in + (long)img * C * P : nullptr;
-    if (a.in_taps) {
-      const float* ytap = a.in_taps + (long)img * M3 * P;
-      const float* mx = a.vmul_x ? a.vmul_x + (long)img * C * P : nullptr;
-      const float* ep = a.dot_eps ? a.dot_eps + (long)img * C * P : nullptr;
-      const float msp = a.vmul_x ? softplus_f(ldc(a.vmul_beta)) : 0.f;
-      const float* mxp = mx ? mx : ytap;
-      const float* epp = ep ? ep : ytap;
-      float* accw = a.acc_w ? a.acc_w + (long)img * C * P : nullptr;
-      const float* awp = accw ? accw : ytap;
-      auto pass = [&](auto nuc, int i0) {
-        constexpr int NU = decltype(nuc)::value;
-        float tv[NU][9], xm[NU], ev[NU], wv[NU];
-#pragma unroll
-        for (int u = 0; u < NU; ++u) {
-          const int i = i0 + u * KB_NT;
-          const int ic = i < vhn ? i : 0;
-          const int c = ic / (RH * CW), rr = ic - c * RH * CW;
-          const int hy = rr / CW, hx = rr - hy * CW;
-          const int yq = min(max(y0 + hy - 1, 0), a.H - 1), xq = min(max(x0 + hx - 1, 0), W - 1);
-          const long ee = (long)c * P + yq * W + xq;
-          const float* yc = ytap + (long)c * 9 * P;
-#pragma unroll
-          for (int tp = 0; tp < 9; ++tp) {
-            const int y2 = min(max(yq + tp / 3 - 1, 0), a.H - 1), x2 = min(max(xq + tp % 3 - 1, 0), W - 1);
-            tv[u][tp] = yc[(long)tp * P + y2 * W + x2];
-          }
-          // (side inputs only where the net has them: a dummy load still costs a slot in the wave's load queue)
-          xm[u] = mx ? mxp[ee] : 0.f;
-          ev[u] = ep ? epp[ee] : 0.f;
-          wv[u] = accw ? awp[ee] : 0.f;
-        }
-        if (early_pending && i0 - tid + KB_NT * NU >= vhz) issue_early();   // after the last pass's loads
-#pragma unroll
-        for (int u = 0; u < NU; ++u) {
-          const int i = i0 + u * KB_NT;
-          const int ic = i < vhn ? i : 0;
-          const int c = ic / (RH * CW), rr = ic - c * RH * CW;
-          const int hy = rr / CW, hx = rr - hy * CW;
-          const int yy = y0 + hy - 1, xx = x0 + hx - 1;
-          const bool in_img = i < vhn && yy >= 0 && yy < a.H && xx >= 0 && xx < W;
-          const int ok = in_img ? ((hy >= 1 && hy <= rows && hx >= 1 && hx <= seg) ? 2 : 1) : 0;
-          float v = 0.f;
-#pragma unroll
-          for (int tp = 0; tp < 9; ++tp) {
-            const int y2 = yy + tp / 3 - 1, x2 = xx + tp % 3 - 1;
-            const bool vt = y2 >= 0 && y2 < a.H && x2 >= 0 && x2 < W;
-            v += vt ? tv[u][tp] : 0.f;
-          }
-          if (mx) v = v * swish_fast_d(xm[u], msp);
-          v = ok ? v : 0.f;
-          if (ep && ok == 2) dacc += (double)v * (double)ev[u];
-          if (accw && ok == 2) accw[(long)c * P + yy * W + xx] = fmaf(a.acc_coef, v, wv[u]);
-          hmx = fmaxf(hmx, fabsf(v));
-          if (i < vhz) vh[i] = v;
-        }
-      };
-      constexpr int SU = 4;
-      for (int i0 = tid; i0 < vhz; i0 += KB_NT * SU) {
-        const int nu = min(SU, (vhz - (i0 - tid) + KB_NT - 1) / KB_NT);     // wave-uniform
-        if (nu >= 4) pass(std::integral_constant<int, 4>(), i0);
-        else if (nu == 3) pass(std::integral_constant<int, 3>(), i0);
-        else if (nu == 2) pass(std::integral_constant<int, 2>(), i0);
-        else pass(std::integral_constant<int, 1>(), i0);
-      }
-    } else {
-      const float pre_sp = a.pre_beta ? softplus_f(ldc(a.pre_beta)) : 0.f;
-      // (as fused313.hip: every element's load from a clamped address issued before any is used)
-      constexpr int FU = 4;
-      for (int i0 = tid; i0 < vhz; i0 += KB_NT * FU) {
-        float lv[FU];
-        bool ok[FU];
-#pragma unroll
-        for (int u = 0; u < FU; ++u) {
-          const int i = i0 + u * KB_NT;
-          const int ic = i < vhn ? i : 0;
-          const int c = ic / (RH * CW), rr = ic - c * RH * CW;
-          const int hy = rr / CW, hx = rr - hy * CW;
-          const int yy = y0 + hy - 1, xx = x0 + hx - 1;
-          ok[u] = i < vhn && yy >= 0 && yy < a.H && xx >= 0 && xx < W;
-          lv[u] = in[(long)c * P + min(max(yy, 0), a.H - 1) * W + min(max(xx, 0), W - 1)];
-        }
-#pragma unroll
-        for (int u = 0; u < FU; ++u) {
-          const int i = i0 + u * KB_NT;
-          float v = 0.f;
-          if (ok[u]) {
-            v = lv[u];
-            if (a.pre_beta) v = swish_fast_f(v, pre_sp);
-          }
-          hmx = fmaxf(hmx, fabsf(v));
-          if (i < vhz) vh[i] = v;
-        }
-      }
-    }
-  }
-  {
-    const float w = wave_max(hmx);
-    if (lane == 0) hmax[wid] = w;
-  }
-  if (a.dot_part) {
-    const double w = wave_sum(dacc);
-    if (lane == 0) red[wid] = w;
-  }
-  for (int k = tid; k < K1pad; k += KB_NT) {
-    int o = vhn;                                    // zero run for the K padding
-    if (k < 9 * C) {
-      const int c = k / 9, tt = k - c * 9;
-      o = c * RH * CW + (tt / 3) * CW + (tt % 3);
-    }
-    koff[k] = o;
-  }
+  stage_halo<KB_NT, 4, false>(a, hg, tid, vh, hmx, dacc, [&](bool last) {
+    if (early_pending && last) issue_early();
+  });
+  put_wave_max(lane, wid, hmx, hmax);
+  put_wave_dot(a, lane, wid, dacc, red);
+  fill_koff<KB_NT>(hg, tid, koff);
   int pix[KB_NB];
 #pragma unroll
   for (int b = 0; b < KB_NB; ++b) {
@@ -319,37 +176,25 @@ __global__ __launch_bounds__(512) void net313k_kernel(Net313Pair pr) {
   }
   __syncthreads();
   KSTAMP(1);
-  if (a.dot_part && tid == 0) {
-    double s = 0.0;
-#pragma unroll
-    for (int w = 0; w < KB_NW; ++w) s += red[w];
-    a.dot_part[(long)img * a.dot_nchunk + tile] = s;
-  }
+  write_dot_part<KB_NW>(a, hg, tid, red);
   // phase A scale: one per tile (halo max over all waves)
   float sA;
   int eA;
-  {
-    float m_ = 0.f;
-#pragma unroll
-    for (int w = 0; w < KB_NW; ++w) m_ = fmaxf(m_, hmax[w]);
-    const int sc = h3_scale_exp(m_);
-    sA = __builtin_amdgcn_ldexpf(1.f, sc);
-    eA = -(sc + ldc(a.Ah_exp));
-  }
+  phaseA_scale<KB_NW>(a, hmax, sA, eA);
   // Phase A's im2col operand pre-split (INF_OPT_FUSED_PRESPLIT; the 3-channel scales, where its planes fit beside the
   // halo): the B fragments of phase A are the same for both chunks and every wave (only the weight rows differ), so
   // they are gathered from the halo and split into their fp16 (h, l) planes once per workgroup, one (K tile, column
   // block, lane) slot per thread, instead of 8 gathered ds_read_b32 and the split per wave, K tile, column block and
   // chunk.  Same scale, same rounding: bitwise the same results.
-  constexpr int SEGc = WT ? kb_seg(WT) : 1, ROWSc = KB_BN / SEGc;
+  constexpr int SEGc = WT ? tile_seg(WT, KB_BN) : 1, ROWSc = KB_BN / SEGc;
   constexpr int VHZc = CT * (ROWSc + 2) * (SEGc + 2) + ROWSc * (SEGc + 2);
   constexpr int VH_OFF = KB_CHUNK + KB_NW * KB_BN + 8 + 2 * KB_NW + 4 + (9 * CT + 15) / 16 * 16;
-  constexpr bool PSA = K128_PSA && CT > 0 && WT > 0 && VH_OFF + ((VHZc + 3) & ~3) + NKT1 * KB_NB * 512 <= KB_LDS;
+  constexpr bool PSA = CT > 0 && WT > 0 && VH_OFF + ((VHZc + 3) & ~3) + NKT1 * KB_NB * 512 <= KB_LDS;
   constexpr bool psa = PSA;           // (compile-time: a runtime switch costs the VJP 17 more spilled VGPRs)
   // Where the planes do not fit beside the halo (the 12-channel scales: 56 KiB), chunk 0's phase A takes them from the
-  // chunk buffer, which its put only writes after the column-maxima barrier that ends phase A (K128_PSA0); chunk 1
-  // gathers and splits per wave as before
-  constexpr bool psa0 = K128_PSA0 && !PSA && CT > 0 && WT > 0 && NKT1 * KB_NB * 512 <= KB_CHUNK;
+  // chunk buffer, which its put only writes after the column-maxima barrier that ends phase A; chunk 1 gathers and
+  // splits per wave as before
+  constexpr bool psa0 = !PSA && CT > 0 && WT > 0 && NKT1 * KB_NB * 512 <= KB_CHUNK;
   u32x4* const pa = psa0 ? cb : reinterpret_cast<u32x4*>(vh + ((vhz + 3) & ~3));
   if constexpr (psa || psa0) {
     for (int s_ = tid; s_ < NKT1 * KB_NB * 64; s_ += KB_NT) {
@@ -644,14 +489,6 @@ __global__ __launch_bounds__(512) void net313k_kernel(Net313Pair pr) {
             for (int k1 = 0; k1 < NKT1; ++k1) ldw2(A1h, (long)(8 + wid) * NKT1 + k1, lane, wA1[k1]);
           }
         }
-        if constexpr (c == 0 && K128_D2EARLY) {
-          // chunk 1's first two d2 column blocks behind them, so their HBM latency runs under the last two K steps'
-          // MFMAs (the remaining waits of the loop are for weight loads issued before: vmcnt retires in order)
-          if (kt == 14) {
-            loadD2(1, 0, 2);
-            __builtin_amdgcn_sched_barrier(0);         // (kept ahead of the step's MFMAs: the scheduler sank them)
-          }
-        }
         mmr(wa, hb, lb, kt + 1);
         if (kt + 2 < 16) ldW(kt + 2, wa);
         mmr(wb, hb, lb, min(kt + 2, 15));
@@ -660,7 +497,9 @@ __global__ __launch_bounds__(512) void net313k_kernel(Net313Pair pr) {
     if constexpr (c == 0) {
       KSTAMP(4);
       KSUB(0);
-      if constexpr (!K128_D2EARLY) loadD2(1, 0, 2);
+      // (measured and not kept: these loads issued in phase B's last K step instead, 16.83 / 16.89 vs 16.81 / 16.75 ms
+      // per step on one box)
+      loadD2(1, 0, 2);
     }
   };
   chunk(std::integral_constant<int, 0>());

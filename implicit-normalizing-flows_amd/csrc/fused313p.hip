@@ -18,9 +18,7 @@
 // Chunk 1's values go into the buffer at chunk 0's column scales when they fit fp16 there, else the exact-scale path
 // (parking in the wave's own 16 KiB of the buffer, column maxima, one scale per column over the chunk) -- the
 // arithmetic and scale rules of fused313k.hip, so the results agree with it to fp32 roundoff.
-#include <type_traits>
-
-#include "kernels.h"
+#include "fused313_stage.h"
 
 namespace inf {
 
@@ -32,35 +30,13 @@ constexpr int PB_NT = 64 * PB_NW;
 constexpr int PB_HID = 512;
 constexpr int PB_CHUNK = 16384;     // floats: 16 K tiles x 2 column blocks x 2 planes x 64 lanes x 16 B
 constexpr int PB_LDS = 19968;       // floats (78 KiB): two workgroups per CU
-
-__device__ __forceinline__ void ldw2p(const u32x4* base, long tile, int lane, u32x4 (&o)[2]) {
-  const u32x4* q = base + tile * 2 * 64 + lane;
-  o[0] = q[0];
-  o[1] = q[64];
-}
-
-__device__ __forceinline__ void split4p(float v0, float v1, float v2, float v3, float S, uint2& h, uint2& l) {
-  const _Float16 h0 = (_Float16)(v0 * S), h1 = (_Float16)(v1 * S), h2 = (_Float16)(v2 * S), h3 = (_Float16)(v3 * S);
-  const _Float16 l0 = (_Float16)__builtin_fmaf(v0, S, -(float)h0), l1 = (_Float16)__builtin_fmaf(v1, S, -(float)h1);
-  const _Float16 l2 = (_Float16)__builtin_fmaf(v2, S, -(float)h2), l3 = (_Float16)__builtin_fmaf(v3, S, -(float)h3);
-  const f16x2 a = {h0, h1}, b = {h2, h3}, c = {l0, l1}, d = {l2, l3};
-  h = make_uint2(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b));
-  l = make_uint2(__builtin_bit_cast(unsigned, c), __builtin_bit_cast(unsigned, d));
-}
-
-constexpr int pb_seg(int W) { return W < PB_BN ? W : PB_BN; }
 }  // namespace
 
 int net313p_fits(int hid, int C, int H, int W) {
   if (hid != PB_HID) return 0;
-  const int P = H * W;
-  const int seg = W < PB_BN ? W : PB_BN;
-  if (P % PB_BN != 0 || PB_BN % seg != 0 || (W > PB_BN && W % PB_BN != 0) || seg % 4 != 0) return 0;
+  if (!halo_tiles(H, W, PB_BN) || tile_seg(W, PB_BN) % 4 != 0) return 0;
   if (9 * C > 256) return 0;                      // phase A: at most 16 K tiles
-  const int rows = PB_BN / seg;
-  const long k1pad = (9L * C + 15) / 16 * 16;
-  const long need = PB_CHUNK + PB_NW * PB_BN + 8 + 2 * PB_NW + 4 + k1pad + (long)C * (rows + 2) * (seg + 2) +
-                    (long)rows * (seg + 2);
+  const long need = PB_CHUNK + PB_NW * PB_BN + 8 + 2 * PB_NW + 4 + halo_lds_floats(C, W, PB_BN);
   return need <= PB_LDS;
 }
 
@@ -75,7 +51,7 @@ __global__ __launch_bounds__(PB_NT) __attribute__((amdgpu_waves_per_eu(2))) void
   const int li = lane & 31, lh = lane >> 5;
   const int C = CT ? CT : a.C;
   const int W = WT ? WT : a.W;
-  const int seg = WT ? pb_seg(WT) : a.seg;
+  const int seg = WT ? tile_seg(WT, PB_BN) : a.seg;
   const int rows = PB_BN / seg;
   const int K1pad = CT ? (9 * CT + 15) / 16 * 16 : a.K1pad;
   const int M3 = 9 * C;
@@ -85,9 +61,8 @@ __global__ __launch_bounds__(PB_NT) __attribute__((amdgpu_waves_per_eu(2))) void
   const int img = bid / tiles_per_img, tile = bid - img * tiles_per_img;
   const int p0 = tile * PB_BN;
   const int y0 = p0 / W, x0 = p0 - y0 * W;
-  const int RH = rows + 2, CW = seg + 2;
-  const int vhn = C * RH * CW;
-  const int vhz = vhn + rows * CW;                  // zero run for the K-padding rows of phase A
+  const HaloGeom hg{C, a.H, W, seg, rows, K1pad, img, tile, y0, x0};
+  const int CW = hg.CW();
   // LDS: chunk buffer | column maxima [NW][BN] | halo maxima [8] | trace partials [NW] (fp64) | flags [4] | koff | halo
   u32x4* cb = reinterpret_cast<u32x4*>(smem);
   float* cmax = smem + PB_CHUNK;
@@ -103,107 +78,13 @@ __global__ __launch_bounds__(PB_NT) __attribute__((amdgpu_waves_per_eu(2))) void
     return reinterpret_cast<const f32x4*>(base + ((tile64 * 16 + rb) * 2 + b) * 1024 + lane * 16);
   };
 
-  // ---- stage the input halo tile ----
+  // ---- stage the input halo tile (fused313_stage.h) ----
   float hmx = 0.f;
   double dacc = 0.0;
-  {
-    const float* in = a.in ? a.in + (long)img * C * P : nullptr;
-    if (a.in_taps) {
-      const float* ytap = a.in_taps + (long)img * M3 * P;
-      const float* mx = a.vmul_x ? a.vmul_x + (long)img * C * P : nullptr;
-      const float* ep = a.dot_eps ? a.dot_eps + (long)img * C * P : nullptr;
-      const float msp = a.vmul_x ? softplus_f(ldc(a.vmul_beta)) : 0.f;
-      const float* mxp = mx ? mx : ytap;
-      const float* epp = ep ? ep : ytap;
-      float* accw = a.acc_w ? a.acc_w + (long)img * C * P : nullptr;
-      const float* awp = accw ? accw : ytap;
-      auto pass = [&](auto nuc, int i0) {
-        constexpr int NU = decltype(nuc)::value;
-        float tv[NU][9], xm[NU], ev[NU], wv[NU];
-#pragma unroll
-        for (int u = 0; u < NU; ++u) {
-          const int i = i0 + u * PB_NT;
-          const int ic = i < vhn ? i : 0;
-          const int c = ic / (RH * CW), rr = ic - c * RH * CW;
-          const int hy = rr / CW, hx = rr - hy * CW;
-          const int yq = min(max(y0 + hy - 1, 0), a.H - 1), xq = min(max(x0 + hx - 1, 0), W - 1);
-          const long ee = (long)c * P + yq * W + xq;
-          const float* yc = ytap + (long)c * 9 * P;
-#pragma unroll
-          for (int tp = 0; tp < 9; ++tp) {
-            const int y2 = min(max(yq + tp / 3 - 1, 0), a.H - 1), x2 = min(max(xq + tp % 3 - 1, 0), W - 1);
-            tv[u][tp] = yc[(long)tp * P + y2 * W + x2];
-          }
-          xm[u] = mx ? mxp[ee] : 0.f;
-          ev[u] = ep ? epp[ee] : 0.f;
-          wv[u] = accw ? awp[ee] : 0.f;
-        }
-#pragma unroll
-        for (int u = 0; u < NU; ++u) {
-          const int i = i0 + u * PB_NT;
-          const int ic = i < vhn ? i : 0;
-          const int c = ic / (RH * CW), rr = ic - c * RH * CW;
-          const int hy = rr / CW, hx = rr - hy * CW;
-          const int yy = y0 + hy - 1, xx = x0 + hx - 1;
-          const bool in_img = i < vhn && yy >= 0 && yy < a.H && xx >= 0 && xx < W;
-          const int ok = in_img ? ((hy >= 1 && hy <= rows && hx >= 1 && hx <= seg) ? 2 : 1) : 0;
-          float v = 0.f;
-#pragma unroll
-          for (int tp = 0; tp < 9; ++tp) {
-            const int y2 = yy + tp / 3 - 1, x2 = xx + tp % 3 - 1;
-            const bool vt = y2 >= 0 && y2 < a.H && x2 >= 0 && x2 < W;
-            v += vt ? tv[u][tp] : 0.f;
-          }
-          if (mx) v = v * swish_fast_d(xm[u], msp);
-          v = ok ? v : 0.f;
-          if (ep && ok == 2) dacc += (double)v * (double)ev[u];
-          if (accw && ok == 2) accw[(long)c * P + yy * W + xx] = fmaf(a.acc_coef, v, wv[u]);
-          hmx = fmaxf(hmx, fabsf(v));
-          if (i < vhz) vh[i] = v;
-        }
-      };
-      constexpr int SU = 4;
-      for (int i0 = tid; i0 < vhz; i0 += PB_NT * SU) {
-        const int nu = min(SU, (vhz - (i0 - tid) + PB_NT - 1) / PB_NT);     // wave-uniform
-        if (nu >= 4) pass(std::integral_constant<int, 4>(), i0);
-        else if (nu == 3) pass(std::integral_constant<int, 3>(), i0);
-        else if (nu == 2) pass(std::integral_constant<int, 2>(), i0);
-        else pass(std::integral_constant<int, 1>(), i0);
-      }
-    } else {
-      const float pre_sp = a.pre_beta ? softplus_f(ldc(a.pre_beta)) : 0.f;
-      for (int i = tid; i < vhz; i += PB_NT) {
-        float v = 0.f;
-        if (i < vhn) {
-          const int c = i / (RH * CW), rr = i - c * RH * CW;
-          const int hy = rr / CW, hx = rr - hy * CW;
-          const int yy = y0 + hy - 1, xx = x0 + hx - 1;
-          if (yy >= 0 && yy < a.H && xx >= 0 && xx < W) {
-            v = in[(long)c * P + yy * W + xx];
-            if (a.pre_beta) v = swish_fast_f(v, pre_sp);
-          }
-        }
-        hmx = fmaxf(hmx, fabsf(v));
-        vh[i] = v;
-      }
-    }
-  }
-  {
-    const float w = wave_max(hmx);
-    if (lane == 0) hmax[wid] = w;
-  }
-  if (a.dot_part) {
-    const double w = wave_sum(dacc);
-    if (lane == 0) red[wid] = w;
-  }
-  for (int k = tid; k < K1pad; k += PB_NT) {
-    int o = vhn;                                    // zero run for the K padding
-    if (k < 9 * C) {
-      const int c = k / 9, tt = k - c * 9;
-      o = c * RH * CW + (tt / 3) * CW + (tt % 3);
-    }
-    koff[k] = o;
-  }
+  stage_halo<PB_NT, 4, false>(a, hg, tid, vh, hmx, dacc, [](bool) {});
+  put_wave_max(lane, wid, hmx, hmax);
+  put_wave_dot(a, lane, wid, dacc, red);
+  fill_koff<PB_NT>(hg, tid, koff);
   int pix[PB_NB];
 #pragma unroll
   for (int b = 0; b < PB_NB; ++b) {
@@ -212,22 +93,10 @@ __global__ __launch_bounds__(PB_NT) __attribute__((amdgpu_waves_per_eu(2))) void
     pix[b] = py * CW + (n - py * seg);
   }
   __syncthreads();
-  if (a.dot_part && tid == 0) {
-    double s = 0.0;
-#pragma unroll
-    for (int w = 0; w < PB_NW; ++w) s += red[w];
-    a.dot_part[(long)img * a.dot_nchunk + tile] = s;
-  }
+  write_dot_part<PB_NW>(a, hg, tid, red);
   float sA;
   int eA;
-  {
-    float m_ = 0.f;
-#pragma unroll
-    for (int w = 0; w < PB_NW; ++w) m_ = fmaxf(m_, hmax[w]);
-    const int sc = h3_scale_exp(m_);
-    sA = __builtin_amdgcn_ldexpf(1.f, sc);
-    eA = -(sc + ldc(a.Ah_exp));
-  }
+  phaseA_scale<PB_NW>(a, hmax, sA, eA);
   const u32x4* A1h = reinterpret_cast<const u32x4*>(a.A1h);
   const u32x4* A2h = reinterpret_cast<const u32x4*>(a.A2h);
   const u32x4* A3p = reinterpret_cast<const u32x4*>(a.A3p);
@@ -240,7 +109,7 @@ __global__ __launch_bounds__(PB_NT) __attribute__((amdgpu_waves_per_eu(2))) void
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       uint2 h, l;
-      split4p(v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3], S, h, l);
+      split4h(v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3], S, h, l);
       const int kt = kt0 + (g >> 1);
       const int base = ((kt * PB_NB + b) * 2) * 64 + 32 * (g & 1) + li;
       reinterpret_cast<uint2*>(cb + base)[lh] = h;
@@ -286,18 +155,18 @@ __global__ __launch_bounds__(PB_NT) __attribute__((amdgpu_waves_per_eu(2))) void
     if constexpr (NKT1 > 0 && NKT1 <= 2) {
       u32x4 wA[NKT1][2];
 #pragma unroll
-      for (int kt = 0; kt < NKT1; ++kt) ldw2p(A1h, (long)rbA * NKT1 + kt, lane, wA[kt]);
+      for (int kt = 0; kt < NKT1; ++kt) ldw2(A1h, (long)rbA * NKT1 + kt, lane, wA[kt]);
 #pragma unroll
       for (int kt = 0; kt < NKT1; ++kt) stepA(kt, wA[kt]);
     } else {
       u32x4 w0[2], w1[2];
-      ldw2p(A1h, (long)rbA * nkt1, lane, w0);
+      ldw2(A1h, (long)rbA * nkt1, lane, w0);
 #pragma unroll 1
       for (int kt = 0; kt < nkt1; kt += 2) {
         const bool has1 = kt + 1 < nkt1;
-        if (has1) ldw2p(A1h, (long)rbA * nkt1 + kt + 1, lane, w1);
+        if (has1) ldw2(A1h, (long)rbA * nkt1 + kt + 1, lane, w1);
         stepA(kt, w0);
-        if (kt + 2 < nkt1) ldw2p(A1h, (long)rbA * nkt1 + kt + 2, lane, w0);
+        if (kt + 2 < nkt1) ldw2(A1h, (long)rbA * nkt1 + kt + 2, lane, w0);
         if (has1) stepA(kt + 1, w1);
       }
     }
@@ -329,7 +198,7 @@ __global__ __launch_bounds__(PB_NT) __attribute__((amdgpu_waves_per_eu(2))) void
   auto phaseB = [&](int c) {
     auto ldW = [&](int kt, u32x4 (&o)[4][2]) {
 #pragma unroll
-      for (int m = 0; m < 4; ++m) ldw2p(A2h, (long)(4 * wid + m) * 32 + 16 * c + kt, lane, o[m]);
+      for (int m = 0; m < 4; ++m) ldw2(A2h, (long)(4 * wid + m) * 32 + 16 * c + kt, lane, o[m]);
     };
     auto mm = [&](int kt, const u32x4 (&w)[4][2]) {
       u32x4 hb[PB_NB], lb[PB_NB];
@@ -503,13 +372,13 @@ __global__ __launch_bounds__(PB_NT) __attribute__((amdgpu_waves_per_eu(2))) void
 #pragma unroll
       for (int r = 0; r < 16; ++r) cacc[b][r] = 0.f;
     u32x4 w3a[2], w3b[2];
-    ldw2p(A3p, (long)rb * 32 + 8 * wid, lane, w3a);
+    ldw2(A3p, (long)rb * 32 + 8 * wid, lane, w3a);
 #pragma unroll
     for (int kk = 0; kk < 8; kk += 2) {
-      ldw2p(A3p, (long)rb * 32 + 8 * wid + kk + 1, lane, w3b);
+      ldw2(A3p, (long)rb * 32 + 8 * wid + kk + 1, lane, w3b);
 #pragma unroll
       for (int b = 0; b < PB_NB; ++b) cacc[b] = mfma_h3(w3a, bh[kk][b], bl[kk][b], cacc[b]);
-      if (kk + 2 < 8) ldw2p(A3p, (long)rb * 32 + 8 * wid + kk + 2, lane, w3a);
+      if (kk + 2 < 8) ldw2(A3p, (long)rb * 32 + 8 * wid + kk + 2, lane, w3a);
 #pragma unroll
       for (int b = 0; b < PB_NB; ++b) cacc[b] = mfma_h3(w3b, bh[kk + 1][b], bl[kk + 1][b], cacc[b]);
     }

@@ -187,7 +187,7 @@ struct Net313Args {
   const void* A2s;
   const void* A3s;
   // A1h / A2h / A3h: the operands as two scaled fp16 planes (h, l) per fragment tile, scales 2^Ah_exp[0..2]
-  // (common.h split2h); non-null (with A1s..A3s) selects INF_MFMA_F16X3 (h3 in phase B, and in A / C with H3_AC)
+  // (common.h split2h); non-null (with A1s..A3s) selects INF_MFMA_F16X3 (h3 in all three phases)
   const void* A1h;
   const void* A2h;
   const void* A3h;
@@ -227,15 +227,9 @@ struct Net313Pair {
   int dbg;                // bit 16: the 128-pixel kernel's chunk-1 exact-scale path on every tile (results unchanged);
                           // bit 32: the wide 32-pixel kernel splits its B operands per consuming wave (no pre-split)
   int reverse;            // 128-pixel kernel: workgroup i runs tile nb - 1 - i (alternating series terms)
-  int xcd;                // two nets, 8 | grid: blocks b with (b & 7) < 4 run net 0, the others net 1 (blocks b and
-                          // b + 8 share an XCD, MI355X_MICROARCH.md), so each XCD's L2 holds one net's weight planes
 };
 // (net, tile) of a pair launch's workgroup `bx` (after any reversal); speed-only placement, results do not depend on it
 __device__ __forceinline__ int pair_tile(const Net313Pair& pr, int bx, int& sel) {
-  if (pr.xcd) {
-    sel = (bx & 7) >> 2;
-    return (bx >> 3) * 4 + (bx & 3);
-  }
   sel = bx >= pr.nb0 ? 1 : 0;
   return bx - (sel ? pr.nb0 : 0);
 }

@@ -1027,10 +1027,6 @@ __global__ __launch_bounds__(256 * BR_FUSED_CH) void broyden_fused_kernel(Broyde
   }
 }
 
-#ifndef BR_FUSED
-#define BR_FUSED 1      // 0: the chunked four-launch update for every d (A/B builds)
-#endif
-
 int launch_broyden_update(const BroydenArgs& a, hipStream_t s) {
   if (a.T > BR_TMAX || a.m >= a.T || a.ncols > a.T) return INF_ERR_INVALID;
   // algorithmic bytes (fp32, D = batch x d): each kernel's distinct reads and writes of the d-vectors and U / VT columns
@@ -1046,7 +1042,7 @@ int launch_broyden_update(const BroydenArgs& a, hipStream_t s) {
     return INF_OK;
   }
   const int nchunk = (a.d + BR_CH - 1) / BR_CH;
-  if (BR_FUSED && nchunk <= BR_FUSED_CH) {
+  if (nchunk <= BR_FUSED_CH) {
     // dx, dg, gx, x; U_j, VT_j (j < m); writes U_m, VT_m, update, x_new, dx_new
     INF_PROF_LAUNCH(s, 716, D4 * (9.0 + 2.0 * a.m), broyden_fused_kernel, dim3(a.batch), dim3(256 * nchunk), 0, s, a,
                     nchunk);

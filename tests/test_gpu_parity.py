@@ -589,6 +589,63 @@ def test_fused_wide_variant_matches_generic(C, H, hid, B, mfma, monkeypatch):
         _close(a, b, rel=1e-5)
 
 
+def _k128_policies_match_64px(net, x, v, exact_scale=0):
+    """Body of the INF_OPT_FUSED_K128 policy comparisons: forward, VJP, a 10-term chained series and the Neumann vector
+    of `net` (INF_MFMA_F16X3) under policies 2, 3 and 0, workspace and LDS NaN-poisoned before every call; policies 2
+    and 3 finite and within 1e-5 of max(1, |ref|_inf) of policy 0.  Returns the launch-profile tags seen per policy."""
+    B = x.shape[0]
+    eps = torch.sign(v)
+    _hip.check(net.lib.inf_net_set_mfma(net.handle, 2), 'set_mfma')
+    stream = _hip.stream_of(x)
+    net.refresh_if_needed(stream)
+    ws = _hip.workspace(x.device, net.ws_bytes(B))
+    n = 10
+    co = np.array([(-1) ** (k + 1) / k for k in range(1, n + 1)], dtype=np.float32)
+    nco = np.array([(-1) ** k * (1.0 if k < 8 else 0.5) for k in range(n + 1)], dtype=np.float32)
+    fptr = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+
+    def poison():
+        ws.fill_(255)
+        _hip.check(net.lib.inf_debug_poison_lds(stream), 'poison_lds')
+    outs, tags = {}, {}
+    k_prev = net.get_option(_hip.INF_OPT_FUSED_K128)
+    assert net.set_option(_hip.INF_OPT_K128_EXACT_SCALE, exact_scale) == 0
+    try:
+        for pol in (2, 3, 0):
+            prev = net.set_option(_hip.INF_OPT_FUSED_K128, pol)
+            assert prev in (0, 1, 2, 3)
+            y, g, ld, w = torch.empty_like(x), torch.empty_like(x), torch.empty(B, device=DEV), torch.empty_like(x)
+            _hip.profile_begin(1000)
+            try:
+                poison()
+                _hip.check(net.lib.inf_net_forward(net.handle, _hip.ptr(x), _hip.ptr(y), B, _hip.ptr(ws), ws.numel(),
+                                                   stream), 'fwd')
+                poison()
+                _hip.check(net.lib.inf_net_vjp(net.handle, _hip.ptr(x), _hip.ptr(v), _hip.ptr(g), B, _hip.ptr(ws),
+                                               ws.numel(), stream), 'vjp')
+                poison()
+                _hip.check(net.lib.inf_logdet_series(net.handle, _hip.ptr(x), _hip.ptr(eps), fptr(co), n, _hip.ptr(ld),
+                                                     B, _hip.ptr(ws), ws.numel(), stream), 'series')
+                poison()
+                _hip.check(net.lib.inf_neumann_vector(net.handle, _hip.ptr(x), _hip.ptr(eps), fptr(nco), n, _hip.ptr(w),
+                                                      B, _hip.ptr(ws), ws.numel(), stream), 'neumann')
+                torch.cuda.synchronize()
+            finally:
+                tags[pol] = {s_['tag'] for s_ in _hip.profile_end()}
+            outs[pol] = (y, g, ld, w)
+    finally:
+        net.set_option(_hip.INF_OPT_FUSED_K128, k_prev)
+        net.set_option(_hip.INF_OPT_K128_EXACT_SCALE, 0)
+    assert net.lib.inf_net_set_option(net.handle, _hip.INF_OPT_FUSED_K128, 4) < 0
+    assert net.get_option(_hip.INF_OPT_FUSED_K128) == k_prev
+    for pol in (2, 3):          # the 128-pixel kernel; the two-per-CU 64-pixel VJP (fused313p.hip)
+        for a in outs[pol]:
+            assert torch.isfinite(a).all()
+        for a, b in zip(outs[pol], outs[0]):
+            _close(a, b, rel=1e-5)
+    return tags
+
+
 @pytest.mark.parametrize('skew,exact_scale', [(False, 0), (True, 0), (False, 1)])
 @pytest.mark.parametrize('B', [2, 16])
 @pytest.mark.parametrize('block', [0, 1, 3])
@@ -617,52 +674,39 @@ def test_fused_k128_vjp_matches_64px_kernel(block, B, skew, exact_scale):
     torch.manual_seed(7)
     x = (torch.randn(B, *shape) * 0.5).to(DEV)
     v = torch.randn(B, *shape).to(DEV)
-    eps = torch.sign(v)
     net = _hip.native_net(blk.nnet_z, x.shape[1:], x.device)
-    _hip.check(net.lib.inf_net_set_mfma(net.handle, 2), 'set_mfma')
-    stream = _hip.stream_of(x)
-    net.refresh_if_needed(stream)
-    ws = _hip.workspace(x.device, net.ws_bytes(B))
-    n = 10
-    co = np.array([(-1) ** (k + 1) / k for k in range(1, n + 1)], dtype=np.float32)
-    nco = np.array([(-1) ** k * (1.0 if k < 8 else 0.5) for k in range(n + 1)], dtype=np.float32)
-    fptr = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+    _k128_policies_match_64px(net, x, v, exact_scale)
 
-    def poison():
-        ws.fill_(255)
-        _hip.check(net.lib.inf_debug_poison_lds(stream), 'poison_lds')
-    outs = {}
-    k_prev = net.get_option(_hip.INF_OPT_FUSED_K128)
-    assert net.set_option(_hip.INF_OPT_K128_EXACT_SCALE, exact_scale) == 0
-    try:
-        for pol in (2, 3, 0):
-            prev = net.set_option(_hip.INF_OPT_FUSED_K128, pol)
-            assert prev in (0, 1, 2, 3)
-            y, g, ld, w = torch.empty_like(x), torch.empty_like(x), torch.empty(B, device=DEV), torch.empty_like(x)
-            poison()
-            _hip.check(net.lib.inf_net_forward(net.handle, _hip.ptr(x), _hip.ptr(y), B, _hip.ptr(ws), ws.numel(),
-                                               stream), 'fwd')
-            poison()
-            _hip.check(net.lib.inf_net_vjp(net.handle, _hip.ptr(x), _hip.ptr(v), _hip.ptr(g), B, _hip.ptr(ws),
-                                           ws.numel(), stream), 'vjp')
-            poison()
-            _hip.check(net.lib.inf_logdet_series(net.handle, _hip.ptr(x), _hip.ptr(eps), fptr(co), n, _hip.ptr(ld), B,
-                                                 _hip.ptr(ws), ws.numel(), stream), 'series')
-            poison()
-            _hip.check(net.lib.inf_neumann_vector(net.handle, _hip.ptr(x), _hip.ptr(eps), fptr(nco), n, _hip.ptr(w), B,
-                                                  _hip.ptr(ws), ws.numel(), stream), 'neumann')
-            torch.cuda.synchronize()
-            outs[pol] = (y, g, ld, w)
-    finally:
-        net.set_option(_hip.INF_OPT_FUSED_K128, k_prev)
-        net.set_option(_hip.INF_OPT_K128_EXACT_SCALE, 0)
-    assert net.lib.inf_net_set_option(net.handle, _hip.INF_OPT_FUSED_K128, 4) < 0
-    assert net.get_option(_hip.INF_OPT_FUSED_K128) == k_prev
-    for pol in (2, 3):          # the 128-pixel kernel; the two-per-CU 64-pixel VJP (fused313p.hip)
-        for a in outs[pol]:
-            assert torch.isfinite(a).all()
-        for a, b in zip(outs[pol], outs[0]):
-            _close(a, b, rel=1e-5)
+
+@pytest.mark.parametrize('C,H,W,B,lead_swish', [(5, 16, 16, 65, True), (7, 8, 32, 64, True), (5, 16, 16, 65, False)])
+def test_fused_k128_runtime_geometry_matches_64px_kernel(C, H, W, B, lead_swish):
+    """The runtime-geometry instantiations net313k_kernel<*, 0, 0> and net313p_kernel<0, 0> (any (C, W) other than the
+    CIFAR-10 / CelebA-HQ 256 scales, where the halo staging's index arithmetic is not constant-folded) against the
+    64-pixel kernel, as test_fused_k128_vjp_matches_64px_kernel: 512-wide 3-1-3 nets at
+      (5, 16, 16): 9C = 45, so K1pad = 48 and M3pad = 64 (K-padding rows, a padded tap row block), 8-row tiles;
+      (7, 8, 32): seg = W, K1pad = 64;
+      (5, 16, 16) without the leading Swish: the first-block shape (no vmul_x, no pre_beta).
+    The batch is the smallest at which the launcher keeps the 64-pixel variant that policies 2 and 3 replace: below
+    256 64-pixel tiles (B < 64 at 256 pixels per image) it takes the 32-pixel two-per-CU kernel whatever the policy,
+    and neither kernel under test would run (65: an odd batch where the tile count allows it).  The launch profile is
+    checked for net313k_kernel<VJP> / <EVAL> (532 / 530) under policy 2 and net313p_kernel (542) under policy 3."""
+    from lib.layers.base import InducedNormConv2d, Swish
+    torch.manual_seed(3)
+    conv = lambda a, b, k: InducedNormConv2d(a, b, k, 1, k // 2, coeff=0.9, atol=1e-3, rtol=1e-3)
+    mods = [conv(C, 512, 3), Swish(), conv(512, 512, 1), Swish(), conv(512, C, 3)]
+    seq = torch.nn.Sequential(*([Swish()] if lead_swish else []), *mods).to(DEV)
+    with torch.no_grad():
+        seq(torch.zeros(1, C, H, W, device=DEV))
+        for m in seq:
+            if isinstance(m, Swish):
+                m.beta.fill_(0.4)
+    x = (torch.randn(B, C, H, W) * 0.5).to(DEV)
+    v = torch.randn(B, C, H, W).to(DEV)
+    net = _hip.NativeNet(_hip.net_entries(seq), (C, H, W), x.device)
+    tags = _k128_policies_match_64px(net, x, v)
+    assert 532 in tags[2] and 530 in tags[2], sorted(tags[2])
+    assert 542 in tags[3], sorted(tags[3])
+    assert not tags[0] & {530, 532, 542} and 502 in tags[0], sorted(tags[0])
 
 
 def test_eval_overlap_matches_sequential():

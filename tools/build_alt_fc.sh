@@ -1,5 +1,5 @@
 # Alternative libinflow.so with extra compile flags on fcnet_h3.hip only (A/B experiments on the fc kernels):
-#   bash tools/build_alt_fc.sh <name> "<flags>"   ->  altlib/lib_<name>.so  (tools/r5_ab3_power.sh swaps it in)
+#   bash tools/build_alt_fc.sh <name> "<flags>"   ->  altlib/lib_<name>.so  (select it with INFLOW_LIB)
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
 C=$R/implicit-normalizing-flows_amd/csrc

@@ -7,12 +7,12 @@ shipped: the product source stays untouched; a patched copy is compiled into gpu
       nod2   no d2 loads at all (multiplier 1)
       nod1   no d1 loads at all (multiplier 1)
       dsyncN first-round workgroups of every other CU group start N k-cycles late (desynchronised bursts)
-      DNAME=V  #define NAME V ahead of the source (the product's compile-time switches)
       sub    INFLOW_K128_SUBSTAMPS: stamps inside chunk 1 and phase C (results unchanged; sched_barrier fences)
       stamps no patch (the phase stamps only)
 Every alternative library is built with INFLOW_PHASE_STAMPS=1 (fused313.hip / fused313k.hip s_memtime stamps at
 the phase boundaries, printed per kernel at exit); `python tools/build_alt_k128.py stamps stamps` gives the product
 kernels with stamps.  Run with INFLOW_LIB=gpurun_alt/lib_<name>.so (tools/series_only.py).
+(The product source has no build-time A/B switches left to pass through: DESIGN.md §13.)
 """
 import os
 import subprocess
@@ -45,9 +45,6 @@ def patch(src, variants):
                         '    const unsigned long long t0_ = __builtin_amdgcn_s_memtime();\n'
                         '    while (__builtin_amdgcn_s_memtime() - t0_ < %dull) __builtin_amdgcn_s_sleep(64);\n'
                         '  }\n  KSTAMP(0);\n' % d))
-    for v in variants:
-        if v.startswith('D') and '=' in v:  # compile-time switch of the product source, e.g. DK128_EARLY_W3=0
-            src = '#define %s %s\n' % tuple(v[1:].split('=')) + src
     if 'sub' in variants:
         src = '#define INFLOW_K128_SUBSTAMPS 1\n' + src
     for old, new in rep:

@@ -1,6 +1,7 @@
-"""Mean SQ counters per dispatch of the VJP kernels in rocprofv3 --pmc CSVs (tools/r5_pmc_sq_k.sh), with the derived
+"""Mean SQ counters per dispatch of the VJP kernels in rocprofv3 --pmc CSVs (a counter-only run: --pmc with the SQ counters read
+below, one output directory per run, no tracing beside it), with the derived
 fractions: MFMA-busy share of the SIMD cycles, wait / active shares of the wave cycles, mean waves per SIMD.
-    python tools/sq_summary.py gpurun_out/r5_sq_k3_s0 [kernel-name substring, e.g. fcblock_kernel]"""
+    python tools/sq_summary.py <rocprofv3 output dir> [kernel-name substring, e.g. fcblock_kernel]"""
 import collections
 import csv
 import glob
