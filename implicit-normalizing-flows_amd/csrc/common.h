@@ -13,8 +13,12 @@ namespace inf {
 
 constexpr int WAVE = 64;   // CDNA wavefront
 
-// ---- activations (reference: activations.py:7-12 Sin, 64-71 Swish) --------------------------
-enum Act { ACT_NONE = 0, ACT_SWISH = 1, ACT_SIN = 2 };
+// ---- activations (reference: activations.py:7-12 Sin, 64-71 Swish; the parameter-less rest of implicit_flow.py's
+// ACT_FNS table: nn.ELU, nn.Softplus, nn.ReLU at their defaults, LipschitzCube, Identity, Zero) ----------------
+// ACT_NONE is "no activation module"; ACT_IDENTITY is the Identity module (the same function, kept apart so a
+// net's plan mirrors its module list)
+enum Act { ACT_NONE = 0, ACT_SWISH = 1, ACT_SIN = 2, ACT_ELU = 3, ACT_SOFTPLUS = 4, ACT_RELU = 5, ACT_LCUBE = 6,
+           ACT_IDENTITY = 7, ACT_ZERO = 8 };
 
 // torch softplus(beta) with its default threshold 20 (F.softplus).
 __device__ __forceinline__ float softplus_f(float b) { return b > 20.f ? b : log1pf(expf(b)); }
@@ -49,17 +53,100 @@ constexpr float PI_F = 3.141592653589793f;
 __device__ __forceinline__ float sinact_f(float a) { return sinf(TWO_PI_F * a) / PI_F * 0.5f; }
 __device__ __forceinline__ float sinact_d(float a) { return cosf(TWO_PI_F * a); }
 
+// nn.ELU (alpha = 1): a > 0 ? a : expm1(a)
+__device__ __forceinline__ float elu_f(float a) { return a > 0.f ? a : expm1f(a); }
+__device__ __forceinline__ float elu_d(float a) { return a > 0.f ? 1.f : expf(a); }
+
+// nn.Softplus (beta = 1, threshold = 20): softplus_f above; its derivative is the sigmoid below the threshold
+__device__ __forceinline__ float softplus_d(float a) { return a > 20.f ? 1.f : sigmoid_f(a); }
+
+// nn.ReLU
+__device__ __forceinline__ float relu_f(float a) { return fmaxf(a, 0.f); }
+__device__ __forceinline__ float relu_d(float a) { return a > 0.f ? 1.f : 0.f; }
+
+// LipschitzCube (activations.py): a - 2/3 above 1, a + 2/3 below -1, a^3 / 3 between
+__device__ __forceinline__ float lcube_f(float a) {
+  return a >= 1.f ? a - 2.f / 3.f : (a <= -1.f ? a + 2.f / 3.f : a * a * a / 3.f);
+}
+__device__ __forceinline__ float lcube_d(float a) { return fabsf(a) < 1.f ? a * a : 1.f; }
+
+__device__ __forceinline__ float identity_f(float a) { return a; }
+__device__ __forceinline__ float identity_d(float) { return 1.f; }
+__device__ __forceinline__ float zero_f(float) { return 0.f; }
+__device__ __forceinline__ float zero_d(float) { return 0.f; }
+
+// Fast forms of ELU and Softplus in swish_fast_*'s style (v_exp_f32, v_log_f32, v_rcp_f32) for the fused kernels'
+// per-element epilogues.  Absolute error <= ~2e-7 (ELU below 0: exp(a) - 1 against expm1(a), both <= 1 in magnitude;
+// Softplus: log(1 + e^a) against log1p(e^a), where 1 + e^a rounds to 2^-24 relative), against the fused kernels' 1e-5
+// parity bound; the branch points are exact (a > 0 / a > 20 pass a through).
+__device__ __forceinline__ float elu_fast_f(float a) { return a > 0.f ? a : __expf(a) - 1.f; }
+__device__ __forceinline__ float elu_fast_d(float a) { return a > 0.f ? 1.f : __expf(a); }
+__device__ __forceinline__ float softplus_fast_f(float a) { return a > 20.f ? a : __logf(1.f + __expf(a)); }
+__device__ __forceinline__ float softplus_fast_d(float a) { return a > 20.f ? 1.f : sigmoid_fast(a); }
+
+// The fused 3-1-3 kernels' activations other than Swish, by a run-time kind (a kernel-argument field: the switch is
+// wave-uniform): ELU, Softplus in their fast forms, ReLU
+__device__ __forceinline__ float fused_act_f(int act, float a) {
+  switch (act) {
+    case ACT_ELU: return elu_fast_f(a);
+    case ACT_SOFTPLUS: return softplus_fast_f(a);
+    default: return relu_f(a);
+  }
+}
+__device__ __forceinline__ float fused_act_d(int act, float a) {
+  switch (act) {
+    case ACT_ELU: return elu_fast_d(a);
+    case ACT_SOFTPLUS: return softplus_fast_d(a);
+    default: return relu_d(a);
+  }
+}
+
 template <int ACT>
 __device__ __forceinline__ float act_f(float a, float sp) {
   if constexpr (ACT == ACT_SWISH) return swish_f(a, sp);
   else if constexpr (ACT == ACT_SIN) return sinact_f(a);
+  else if constexpr (ACT == ACT_ELU) return elu_f(a);
+  else if constexpr (ACT == ACT_SOFTPLUS) return softplus_f(a);
+  else if constexpr (ACT == ACT_RELU) return relu_f(a);
+  else if constexpr (ACT == ACT_LCUBE) return lcube_f(a);
+  else if constexpr (ACT == ACT_ZERO) return zero_f(a);
   else return a;
 }
 template <int ACT>
 __device__ __forceinline__ float act_d(float a, float sp) {
   if constexpr (ACT == ACT_SWISH) return swish_d(a, sp);
   else if constexpr (ACT == ACT_SIN) return sinact_d(a);
+  else if constexpr (ACT == ACT_ELU) return elu_d(a);
+  else if constexpr (ACT == ACT_SOFTPLUS) return softplus_d(a);
+  else if constexpr (ACT == ACT_RELU) return relu_d(a);
+  else if constexpr (ACT == ACT_LCUBE) return lcube_d(a);
+  else if constexpr (ACT == ACT_ZERO) return zero_d(a);
   else return 1.f;
+}
+
+// The parameter-less activations by a run-time kind (a kernel argument: the switch is wave-uniform).  Swish carries a
+// beta and is never dispatched here; ACT_NONE / ACT_IDENTITY pass through.
+__device__ __forceinline__ float act_any_f(int act, float a) {
+  switch (act) {
+    case ACT_SIN: return sinact_f(a);
+    case ACT_ELU: return elu_f(a);
+    case ACT_SOFTPLUS: return softplus_f(a);
+    case ACT_RELU: return relu_f(a);
+    case ACT_LCUBE: return lcube_f(a);
+    case ACT_ZERO: return 0.f;
+    default: return a;
+  }
+}
+__device__ __forceinline__ float act_any_d(int act, float a) {
+  switch (act) {
+    case ACT_SIN: return sinact_d(a);
+    case ACT_ELU: return elu_d(a);
+    case ACT_SOFTPLUS: return softplus_d(a);
+    case ACT_RELU: return relu_d(a);
+    case ACT_LCUBE: return lcube_d(a);
+    case ACT_ZERO: return 0.f;
+    default: return 1.f;
+  }
 }
 
 // A kernel-constant scalar (scale exponent, activation beta) read through the scalar cache: an s_load counts on

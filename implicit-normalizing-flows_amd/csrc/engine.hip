@@ -83,7 +83,34 @@ struct WLayer {
   const float* act_beta = nullptr;
   Operand f, g;                   // forward, vjp
   float* factor = nullptr;        // device [factor, sigma]
+  float* zb = nullptr;            // bias-free layer: the engine's zero vector (cout floats in InfNet::dev) that b points at
 };
+
+// the activations the fused 3-1-3 conv kernels have a form for (fused313*.hip)
+bool fused_act_kind(int act) { return act == ACT_SWISH || act == ACT_ELU || act == ACT_SOFTPLUS || act == ACT_RELU; }
+
+// Two fused 3-1-3 nets that one pair launch can run: the same hidden width, and both Swish or both of the other fused
+// activations -- the launch picks its instantiation (Swish epilogues reading beta1 / beta2, or the kind switch reading
+// Net313Args::act) once, from the first net.  ELU / Softplus / ReLU mix freely: the kind is a per-net field.
+template <typename Net>
+bool fused_pair(const Net* a, const Net* b) {
+  return a->fused && b->fused && a->fhid == b->fhid && (a->L[0].act == ACT_SWISH) == (b->L[0].act == ACT_SWISH);
+}
+
+// InfLayerKind of an activation -> Act, or -1 for any other kind
+int act_of_kind(int kind) {
+  switch (kind) {
+    case INF_ACT_SWISH: return ACT_SWISH;
+    case INF_ACT_SIN: return ACT_SIN;
+    case INF_ACT_ELU: return ACT_ELU;
+    case INF_ACT_SOFTPLUS: return ACT_SOFTPLUS;
+    case INF_ACT_RELU: return ACT_RELU;
+    case INF_ACT_LCUBE: return ACT_LCUBE;
+    case INF_ACT_IDENTITY: return ACT_IDENTITY;
+    case INF_ACT_ZERO: return ACT_ZERO;
+    default: return -1;
+  }
+}
 
 }  // namespace
 
@@ -284,6 +311,9 @@ Net313Args net313_args(const InfNet* n, const float* in, int B, Bufs& bf, bool v
   memset(&f, 0, sizeof(f));
   f.in = in;
   f.pre_beta = vjp ? nullptr : n->pre_beta;
+  // another fused activation than Swish (ELU / Softplus / ReLU; the eligibility check made all of the net's the same)
+  f.act = n->L[0].act == ACT_SWISH ? 0 : n->L[0].act;
+  f.pre_act = (vjp || n->pre_act == ACT_SWISH) ? 0 : n->pre_act;
   f.A1 = vjp ? n->F1b : n->F1f;
   f.K1pad = n->K1pad;
   f.A2 = vjp ? n->F2b : n->F2f;
@@ -372,6 +402,7 @@ int run_forward(InfNet* n, const float* x, int B, Bufs& bf, int mode, const OutA
     float* out = (l % 2 == 0) ? bf.h0 : bf.h1;
     GemmArgs g = gemm_base(n, w.f, cur, cur_ch, B);
     g.pre_beta = (l == 0) ? n->pre_beta : nullptr;
+    g.pre_act = (l == 0) ? n->pre_act : ACT_NONE;
     set_out(n, g, out, w.cout);
     g.bias = w.b;
     g.act = w.act;
@@ -386,6 +417,7 @@ int run_forward(InfNet* n, const float* x, int B, Bufs& bf, int mode, const OutA
   const WLayer& w = n->L[L - 1];
   GemmArgs g = gemm_base(n, w.f, cur, cur_ch, B);
   g.pre_beta = (L == 1) ? n->pre_beta : nullptr;
+  g.pre_act = (L == 1) ? n->pre_act : ACT_NONE;
   set_out(n, g, bf.Y, w.f.M);
   INF_TRY(launch_gemm(g, w.f.load, EP_STORE, s));
   OutArgs a = *oa;
@@ -422,6 +454,7 @@ int run_vjp(InfNet* n, const float* v, float* vout, const float* xin, const floa
     a.in1 = xin;
     a.out0 = vout;
     a.pre_beta = n->pre_beta;
+    a.pre_act = n->pre_act;
     a.partial = partial;
     a.nchunk = out_nchunk(n->d);
     return launch_conv_out(a, B, s);
@@ -455,6 +488,7 @@ int run_vjp(InfNet* n, const float* v, float* vout, const float* xin, const floa
   a.in1 = xin;
   a.out0 = vout;
   a.pre_beta = n->pre_beta;
+  a.pre_act = n->pre_act;
   a.partial = partial;
   a.nchunk = n->fc ? 1 : out_nchunk(n->d);
   return n->fc ? launch_fc_out(a, B, s) : launch_conv_out(a, B, s);
@@ -1596,6 +1630,10 @@ static int layer_sigma_chain(InfNet* n, int l, const float* dWe, float* dW, Grad
 
 static bool grad_supported(const InfNet* n) {
   if (n->L.empty()) return false;
+  // Swish / Sin only: the parameter-gradient kernels carry these two's second derivatives (grad.hip); a bias-free
+  // layer has no db to write
+  for (const WLayer& w : n->L)
+    if (w.zb) return false;
   for (size_t l = 0; l + 1 < n->L.size(); ++l)
     if (n->L[l].act != ACT_SWISH && n->L[l].act != ACT_SIN) return false;
   if (n->L.back().act != ACT_NONE) return false;
@@ -1666,27 +1704,31 @@ int inf_last_hip_error(void) { return inf::g_last_hip; }
 int inf_net_set_tensors(InfNet* n, const InfNetDesc* desc) {
   if (!n || !desc || desc->n_layers <= 0 || !desc->layers) return INF_ERR_INVALID;
   int i = 0;
-  const bool pre = desc->layers[0].kind == INF_ACT_SWISH || desc->layers[0].kind == INF_ACT_SIN;
-  if (pre != (n->pre_act != ACT_NONE)) return INF_ERR_INVALID;
+  const int pre_kind = act_of_kind(desc->layers[0].kind);
+  const bool pre = pre_kind >= 0;
+  if ((pre ? pre_kind : (int)ACT_NONE) != n->pre_act) return INF_ERR_INVALID;
   if (pre) i = 1;
   size_t l = 0;
   std::vector<WLayer> L = n->L;
-  const float* pre_beta = pre ? desc->layers[0].beta : n->pre_beta;
+  const float* pre_beta = n->pre_act == ACT_SWISH ? desc->layers[0].beta : nullptr;
+  if (n->pre_act == ACT_SWISH && !pre_beta) return INF_ERR_INVALID;
   for (; i < desc->n_layers; ++i) {
     const InfLayerDesc& d = desc->layers[i];
     if (d.kind == INF_LAYER_CONV || d.kind == INF_LAYER_LINEAR) {
       if (l >= L.size()) return INF_ERR_INVALID;
       WLayer& w = L[l++];
       const int ks = d.kind == INF_LAYER_LINEAR ? 1 : d.ksize;
-      if (w.kind != d.kind || w.cin != d.cin || w.cout != d.cout || w.ks != ks || !d.weight || !d.bias || !d.u || !d.v)
+      if (w.kind != d.kind || w.cin != d.cin || w.cout != d.cout || w.ks != ks || !d.weight || !d.u || !d.v)
         return INF_ERR_INVALID;
+      if ((d.bias == nullptr) != (w.zb != nullptr)) return INF_ERR_INVALID;   // bias-free layers stay bias-free
       w.W = d.weight;
-      w.b = d.bias;
+      w.b = d.bias ? d.bias : w.zb;
       w.u = d.u;
       w.v = d.v;
-    } else if (d.kind == INF_ACT_SWISH || d.kind == INF_ACT_SIN) {
-      if (l == 0 || L[l - 1].act != (d.kind == INF_ACT_SWISH ? ACT_SWISH : ACT_SIN)) return INF_ERR_INVALID;
-      L[l - 1].act_beta = d.beta;
+    } else if (act_of_kind(d.kind) >= 0) {
+      if (l == 0 || L[l - 1].act != act_of_kind(d.kind)) return INF_ERR_INVALID;
+      if (d.kind == INF_ACT_SWISH && !d.beta) return INF_ERR_INVALID;
+      L[l - 1].act_beta = d.kind == INF_ACT_SWISH ? d.beta : nullptr;
     } else {
       return INF_ERR_INVALID;
     }
@@ -1708,10 +1750,11 @@ int inf_net_create(const InfNetDesc* desc, InfNet** out) {
   n->d = n->C * n->P;
   int i = 0;
   // leading activation (preact, implicit_flow.py:371-373)
-  if (desc->layers[0].kind == INF_ACT_SWISH || desc->layers[0].kind == INF_ACT_SIN) {
-    n->pre_act = desc->layers[0].kind == INF_ACT_SWISH ? ACT_SWISH : ACT_SIN;
-    n->pre_beta = desc->layers[0].beta;
-    if (n->pre_act != ACT_SWISH) { delete n; return INF_ERR_UNSUPPORTED; }
+  // (pre_beta is set for a leading Swish only; the kernels read the kind of any other from pre_act)
+  if (act_of_kind(desc->layers[0].kind) >= 0) {
+    n->pre_act = act_of_kind(desc->layers[0].kind);
+    n->pre_beta = n->pre_act == ACT_SWISH ? desc->layers[0].beta : nullptr;
+    if (n->pre_act == ACT_SWISH && !n->pre_beta) { delete n; return INF_ERR_INVALID; }
     i = 1;
   }
   for (; i < desc->n_layers; ++i) {
@@ -1728,12 +1771,12 @@ int inf_net_create(const InfNetDesc* desc, InfNet** out) {
       w.v = d.v;
       w.coeff = d.coeff;
       if (w.ks != 1 && w.ks != 3) { delete n; return INF_ERR_UNSUPPORTED; }
-      if (!w.b) { delete n; return INF_ERR_UNSUPPORTED; }
       n->L.push_back(w);
-    } else if (d.kind == INF_ACT_SWISH || d.kind == INF_ACT_SIN) {
+    } else if (act_of_kind(d.kind) >= 0) {
       if (n->L.empty() || n->L.back().act != ACT_NONE) { delete n; return INF_ERR_UNSUPPORTED; }
-      n->L.back().act = d.kind == INF_ACT_SWISH ? ACT_SWISH : ACT_SIN;
-      n->L.back().act_beta = d.beta;
+      if (d.kind == INF_ACT_SWISH && !d.beta) { delete n; return INF_ERR_INVALID; }
+      n->L.back().act = act_of_kind(d.kind);
+      n->L.back().act_beta = d.kind == INF_ACT_SWISH ? d.beta : nullptr;
     } else {
       delete n;
       return INF_ERR_INVALID;
@@ -1741,6 +1784,13 @@ int inf_net_create(const InfNetDesc* desc, InfNet** out) {
   }
   const int L = (int)n->L.size();
   if (L == 0 || n->L.back().act != ACT_NONE) { delete n; return INF_ERR_UNSUPPORTED; }
+  // A leading activation other than Swish is applied by the GEMM loader of the parameter-less family's own
+  // instantiations (gemm.hip EP_ACT_ANY), i.e. where the first layer's activation is of that family too -- every net
+  // ImplicitFlow builds (one activation_fn throughout).  Other mixes are not implemented.
+  if (n->pre_act != ACT_NONE && n->pre_act != ACT_SWISH) {
+    const int a0 = n->L[0].act;
+    if (n->pre_act == ACT_SIN || a0 == ACT_NONE || a0 == ACT_SWISH || a0 == ACT_SIN) { delete n; return INF_ERR_UNSUPPORTED; }
+  }
   n->fc = n->L[0].kind == INF_LAYER_LINEAR;
   if (n->fc) {
     n->d = n->C;
@@ -1786,6 +1836,7 @@ int inf_net_create(const InfNetDesc* desc, InfNet** out) {
       floats += (size_t)op->Mpad * op->Kpad + 64;
     }
     floats += 64;   // factor
+    if (!w.b) floats += (size_t)round_up(w.cout, 64);   // the zero bias of a bias-free layer
     if (last) n->rows_max = std::max(n->rows_max, w.f.M);
     if (first) n->rows_max = std::max(n->rows_max, w.g.M);
   }
@@ -1843,7 +1894,8 @@ int inf_net_create(const InfNetDesc* desc, InfNet** out) {
   {
     const char* off = getenv("INFLOW_NO_FUSED");
     const bool shape_ok = !n->fc && L == 3 && n->L[0].ks == 3 && n->L[1].ks == 1 && n->L[2].ks == 3 &&
-                          n->L[0].act == ACT_SWISH && n->L[1].act == ACT_SWISH &&
+                          fused_act_kind(n->L[0].act) && n->L[1].act == n->L[0].act &&
+                          (n->pre_act == ACT_NONE || n->pre_act == n->L[0].act) &&
                           n->L[0].cout == n->L[1].cin && n->L[1].cin == n->L[1].cout && n->L[1].cout == n->L[2].cin;
     if (shape_ok && !(off && off[0] == '1') && net313_supported(n->L[1].cout, n->C, n->H, n->W)) {
       n->fused = true;
@@ -1920,6 +1972,11 @@ int inf_net_create(const InfNetDesc* desc, InfNet** out) {
     }
     w.factor = p;
     p += 64;
+    if (!w.b) {
+      w.zb = p;
+      w.b = p;
+      p += round_up(w.cout, 64);
+    }
   }
   if (n->fused) {
     float** bufs[] = {&n->F1f, &n->F1b, &n->F2f, &n->F2b, &n->F3f, &n->F3b};
@@ -1973,6 +2030,7 @@ int inf_net_refresh(InfNet* n, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   n->f0_batch = -1;
   for (auto& w : n->L) {
+    if (w.zb) INF_HIP(hipMemsetAsync(w.zb, 0, sizeof(float) * w.cout, s));
     const int H = n->fc ? 1 : (w.ks == 1 ? 1 : n->H), Wd = n->fc ? 1 : (w.ks == 1 ? 1 : n->W);
     INF_TRY(launch_sigma(w.W, w.u, w.v, w.cout, w.cin, w.ks, H, Wd, w.coeff, w.factor,
                          reinterpret_cast<float*>(n->scratch), s));
@@ -2184,8 +2242,9 @@ int series_fused(InfNet* const* nets, const float* const* xs, const float* const
       if (k > 0) {
         v.in = nullptr;
         v.in_taps = (k % 2 == 1) ? bf.Y : bf.Y2;
-        v.vmul_x = n->pre_beta ? xs[i] : nullptr;
+        v.vmul_x = n->pre_act != ACT_NONE ? xs[i] : nullptr;
         v.vmul_beta = n->pre_beta;
+        v.vmul_act = n->pre_act == ACT_SWISH ? 0 : n->pre_act;
         if (wouts) {
           v.acc_w = wouts[i];
           v.acc_coef = ncoeff[k];
@@ -2214,6 +2273,7 @@ int series_fused(InfNet* const* nets, const float* const* xs, const float* const
       a.in1 = xs[i];
       a.out0 = bf.va;
       a.pre_beta = n->pre_beta;
+      a.pre_act = n->pre_act;
       a.nchunk = bf.snchunk;
       INF_TRY(launch_conv_out(a, B, s));
       INF_TRY(glue_axpy_scaled(wouts[i], bf.va, ncoeff[n_terms], (long)B * n->d, s));
@@ -2236,6 +2296,7 @@ int series_fused(InfNet* const* nets, const float* const* xs, const float* const
     a.in1 = xs[i];
     a.out0 = bf.va;
     a.pre_beta = n->pre_beta;
+    a.pre_act = n->pre_act;
     a.partial = bf.part + (size_t)(n_terms - 1) * B * bf.snchunk;
     a.nchunk = bf.snchunk;
     INF_TRY(launch_conv_out(a, B, s));
@@ -2286,7 +2347,7 @@ int inf_imblock_eval(InfNet* nx, InfNet* nz, const float* x, float* z, const flo
   if (!nx || !nz || !x || !z || !eps_x || !eps_z || !coeff || !logdet_x || !logdet_z || B <= 0 || T <= 0 || T > 64 ||
       n_terms < 1 || n_terms > SERIES_MAX || !same_shape(nx, nz))
     return INF_ERR_INVALID;
-  if (!(nx->fused && nz->fused && nx->fhid == nz->fhid)) return INF_ERR_UNSUPPORTED;
+  if (!fused_pair(nx, nz)) return INF_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
   const size_t half = ws_need(nx, B, T), zneed = ws_need(nz, B, 1), xneed = ws_need(nx, B, 1);
   if (!ws || ws_bytes < half + zneed) return INF_ERR_WORKSPACE;
@@ -2682,7 +2743,7 @@ int inf_logdet_series_pair(InfNet* na, const float* xa, const float* ea, InfNet*
     const int st = fc_series(nets2, xs2, es2, coeff, n_terms, outs2, 2, B, (hipStream_t)stream);
     if (st != INF_ERR_UNSUPPORTED) return st;
   }
-  if (!(na->fused && nb->fused && na->fhid == nb->fhid)) {
+  if (!fused_pair(na, nb)) {
     INF_TRY(series_single(na, xa, ea, coeff, n_terms, out_a, B, w0, half, (hipStream_t)stream, false));
     return series_single(nb, xb, eb, coeff, n_terms, out_b, B, w0 + half, half, (hipStream_t)stream, false);
   }
@@ -2744,7 +2805,7 @@ int inf_neumann_vector_pair(InfNet* na, const float* xa, const float* ea, InfNet
   if (!na || !nb || !xa || !xb || !ea || !eb || !ncoeff || !wa || !wb || B <= 0 || n_terms < 0 || !same_shape(na, nb))
     return INF_ERR_INVALID;
   const size_t half = ws_bytes / 2;
-  if (!(na->fused && nb->fused && na->fhid == nb->fhid) || n_terms == 0) {
+  if (!fused_pair(na, nb) || n_terms == 0) {
     INF_TRY(inf_neumann_vector(na, xa, ea, ncoeff, n_terms, wa, B, ws, half, stream));
     return inf_neumann_vector(nb, xb, eb, ncoeff, n_terms, wb, B, reinterpret_cast<char*>(ws) + half, half, stream);
   }

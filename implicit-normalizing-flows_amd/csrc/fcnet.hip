@@ -304,7 +304,7 @@ __global__ __launch_bounds__(64 * NW) void fcnet_kernel(FcArgs a) {
 // no input pre-activation; JAC for d = 2 (toy) and d = 6 (POWER).
 int fcnet_supported(const FcArgs& a, bool jac) {
   if (a.nl < 2 || a.nl > FC_MAXL || a.d < 1 || a.d > FC_DMAX) return 0;
-  if (a.act != ACT_SIN && a.act != ACT_SWISH) return 0;
+  if (!fc_act_fused(a.act)) return 0;
   if (a.L[0].Kpad != 16 || a.L[a.nl - 1].Kpad != FC_H) return 0;
   for (int l = 1; l < a.nl - 1; ++l)
     if (a.L[l].Kpad != FC_H) return 0;
@@ -323,12 +323,9 @@ int launch_fcnet(const FcArgs& a, bool jac, hipStream_t s) {
   const unsigned nb = (unsigned)((a.B + S - 1) / S);
   const bool prof = prof_enabled();
   if (prof) prof_begin_launch(s);
-#define FCL(NCB_, JAC_, CW_, NW_)                                                                                   \
-  do {                                                                                                                \
-    if (a.act == ACT_SIN)                                                                                             \
-      hipLaunchKernelGGL((fcnet_kernel<NCB_, JAC_, ACT_SIN, CW_, NW_>), dim3(nb), dim3(64 * NW_), 0, s, a);           \
-    else hipLaunchKernelGGL((fcnet_kernel<NCB_, JAC_, ACT_SWISH, CW_, NW_>), dim3(nb), dim3(64 * NW_), 0, s, a);      \
-  } while (0)
+#define FCL1(ACT_, NCB_, JAC_, CW_, NW_) \
+  hipLaunchKernelGGL((fcnet_kernel<NCB_, JAC_, ACT_, CW_, NW_>), dim3(nb), dim3(64 * NW_), 0, s, a)
+#define FCL(NCB_, JAC_, CW_, NW_) FC_BY_ACT(a.act, FCL1, NCB_, JAC_, CW_, NW_)
   if (h3) {
     INF_TRY(launch_fcnet_h3(a, jac, s));
   } else {
@@ -338,6 +335,7 @@ int launch_fcnet(const FcArgs& a, bool jac, hipStream_t s) {
     INF_CHECK_LAUNCH();
   }
 #undef FCL
+#undef FCL1
   if (prof) {
     const double T = jac ? a.d + 1 : 1;
     double f = 2.0 * a.d * FC_H * 2 + (double)(a.nl - 2) * 2.0 * FC_H * FC_H;   // per sample and column

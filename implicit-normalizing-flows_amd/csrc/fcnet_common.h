@@ -245,6 +245,10 @@ __device__ __forceinline__ float fc_act_f(float a, float sp) {
     float sn, cs;
     sincos_2pi(a, sn, cs);
     return sn * (0.5f / PI_F);
+  } else if constexpr (ACT == ACT_ELU) {
+    return elu_fast_f(a);
+  } else if constexpr (ACT == ACT_SOFTPLUS) {
+    return softplus_fast_f(a);
   } else {
     return swish_fast_f(a, sp);
   }
@@ -257,10 +261,34 @@ __device__ __forceinline__ void fc_act_fd(float a, float sp, float& f, float& d)
     sincos_2pi(a, sn, cs);
     f = sn * (0.5f / PI_F);
     d = cs;
+  } else if constexpr (ACT == ACT_ELU) {
+    const float e = __expf(a);                       // one v_exp_f32 for both
+    f = a > 0.f ? a : e - 1.f;
+    d = a > 0.f ? 1.f : e;
+  } else if constexpr (ACT == ACT_SOFTPLUS) {
+    const float t = 1.f + __expf(a);                 // log(t) and 1 - 1 / t = sigmoid(a)
+    f = a > 20.f ? a : __logf(t);
+    d = a > 20.f ? 1.f : 1.f - __builtin_amdgcn_rcpf(t);
   } else {
     f = swish_fast_f(a, sp);
     d = swish_fast_d(a, sp);
   }
+}
+
+// The activation kinds the fused fc net kernels (fcnet.hip, fcnet_h3.hip) are instantiated for, as a host dispatch:
+// M(ACT, args...) with ACT a compile-time Act.  (fcblock.hip's block and series kernels keep Sin / Swish only.)
+#define FC_BY_ACT(ACTV_, M_, ...)                                \
+  do {                                                           \
+    switch (ACTV_) {                                             \
+      case ACT_SIN: M_(ACT_SIN, __VA_ARGS__); break;             \
+      case ACT_ELU: M_(ACT_ELU, __VA_ARGS__); break;             \
+      case ACT_SOFTPLUS: M_(ACT_SOFTPLUS, __VA_ARGS__); break;   \
+      case ACT_SWISH: M_(ACT_SWISH, __VA_ARGS__); break;         \
+      default: return INF_ERR_UNSUPPORTED;                       \
+    }                                                            \
+  } while (0)
+inline bool fc_act_fused(int act) {
+  return act == ACT_SIN || act == ACT_SWISH || act == ACT_ELU || act == ACT_SOFTPLUS;
 }
 
 }  // namespace inf

@@ -362,23 +362,16 @@ constexpr int FC_FWD_NCB = 3;   // column blocks per workgroup of the FWD kernel
 int launch_fcnet_h3(const FcArgs& a, bool jac, hipStream_t s) {
   const int S = jac ? 16 : 16 * FC_FWD_NCB;
   const unsigned nb = (unsigned)((a.B + S - 1) / S);
-#define FCH(NCB_, JAC_, DD_)                                                                                     \
-  do {                                                                                                           \
-    if (a.act == ACT_SIN)                                                                                        \
-      hipLaunchKernelGGL((fcnet_h3_kernel<NCB_, JAC_, ACT_SIN, DD_>), dim3(nb), dim3(H3_NT), 0, s, a);           \
-    else hipLaunchKernelGGL((fcnet_h3_kernel<NCB_, JAC_, ACT_SWISH, DD_>), dim3(nb), dim3(H3_NT), 0, s, a);      \
-  } while (0)
+#define FCH1(ACT_, NCB_, JAC_, DD_) \
+  hipLaunchKernelGGL((fcnet_h3_kernel<NCB_, JAC_, ACT_, DD_>), dim3(nb), dim3(H3_NT), 0, s, a)
+#define FCH(NCB_, JAC_, DD_) FC_BY_ACT(a.act, FCH1, NCB_, JAC_, DD_)
   // FWD whose readback event completes with the launch itself (OutArgs::stop_ev; not while profiling, whose events
   // bracket every launch)
   const bool bind = !jac && a.o.stop_ev && !prof_enabled();
-#define FCE(NCB_, DD_)                                                                                           \
-  do {                                                                                                           \
-    if (a.act == ACT_SIN)                                                                                        \
-      hipExtLaunchKernelGGL((fcnet_h3_kernel<NCB_, false, ACT_SIN, DD_>), dim3(nb), dim3(H3_NT), 0, s, nullptr,  \
-                            a.o.stop_ev, 0, a);                                                                  \
-    else hipExtLaunchKernelGGL((fcnet_h3_kernel<NCB_, false, ACT_SWISH, DD_>), dim3(nb), dim3(H3_NT), 0, s,      \
-                               nullptr, a.o.stop_ev, 0, a);                                                      \
-  } while (0)
+#define FCE1(ACT_, NCB_, DD_)                                                                                   \
+  hipExtLaunchKernelGGL((fcnet_h3_kernel<NCB_, false, ACT_, DD_>), dim3(nb), dim3(H3_NT), 0, s, nullptr, a.o.stop_ev, \
+                        0, a)
+#define FCE(NCB_, DD_) FC_BY_ACT(a.act, FCE1, NCB_, DD_)
   if (bind) {
     if (a.d == 6) FCE(FC_FWD_NCB, 6);
     else if (a.d == 2) FCE(FC_FWD_NCB, 2);
@@ -389,6 +382,7 @@ int launch_fcnet_h3(const FcArgs& a, bool jac, hipStream_t s) {
     return INF_OK;
   }
 #undef FCE
+#undef FCE1
   if (!jac) {
     if (a.d == 6) FCH(FC_FWD_NCB, false, 6);
     else if (a.d == 2) FCH(FC_FWD_NCB, false, 2);
@@ -400,6 +394,7 @@ int launch_fcnet_h3(const FcArgs& a, bool jac, hipStream_t s) {
     FCH(7, true, 0);
   }
 #undef FCH
+#undef FCH1
   INF_CHECK_LAUNCH();
   return INF_OK;
 }
@@ -410,14 +405,12 @@ int launch_fcnet_h3_jac_pair(const FcArgs& a0, const FcArgs& a1, hipStream_t s) 
   p.a[1] = a1;
   p.nb0 = (a0.B + 15) / 16;
   const unsigned nb = (unsigned)(p.nb0 + (a1.B + 15) / 16);
-#define FCP(NCB_)                                                                                                \
-  do {                                                                                                           \
-    if (a0.act == ACT_SIN) hipLaunchKernelGGL((fcnet_h3_pair_kernel<NCB_, ACT_SIN>), dim3(nb), dim3(H3_NT), 0, s, p); \
-    else hipLaunchKernelGGL((fcnet_h3_pair_kernel<NCB_, ACT_SWISH>), dim3(nb), dim3(H3_NT), 0, s, p);          \
-  } while (0)
+#define FCP1(ACT_, NCB_) hipLaunchKernelGGL((fcnet_h3_pair_kernel<NCB_, ACT_>), dim3(nb), dim3(H3_NT), 0, s, p)
+#define FCP(NCB_) FC_BY_ACT(a0.act, FCP1, NCB_)
   if (a0.d == 2) FCP(3);
   else FCP(7);
 #undef FCP
+#undef FCP1
   INF_CHECK_LAUNCH();
   return INF_OK;
 }

@@ -87,7 +87,8 @@ __device__ __forceinline__ long frag_off(int rb, int kt, int nkt, int lane) {
 
 // SPL: 0 exact fp32 MFMA, 1 split-bf16 (x6) in all phases, 2 x6 in phases A / C and the scaled fp16 split
 // (h3, common.h) in phase B (INF_MFMA_F16X3)
-template <int TM, int MODE, int F_BN, int F_LDS_FLOATS, int SPL = 0, int NW = 8>
+// ACTK: 0 Swish (beta1 / beta2), 1 the other fused activations by Net313Args::act (forward modes only)
+template <int TM, int MODE, int F_BN, int F_LDS_FLOATS, int SPL = 0, int NW = 8, int ACTK = 0>
 __device__ __forceinline__ void net313_body(const Net313Pair& pr) {
   constexpr int NT = 64 * NW;                        // threads per workgroup
   constexpr bool H3 = SPL == 2;
@@ -433,7 +434,7 @@ __device__ __forceinline__ void net313_body(const Net313Pair& pr) {
   STAMP(2);
   // epilogue A -> t (LDS); SAVE: d1 -> HBM
   {
-    const float sp1 = (MODE != MODE_VJP) ? softplus_f(ldc(a.beta1)) : 0.f;
+    const float sp1 = (MODE != MODE_VJP && ACTK == 0) ? softplus_f(ldc(a.beta1)) : 0.f;
     float cm[NB];
 #pragma unroll
     for (int b = 0; b < NB; ++b) cm[b] = 0.f;
@@ -450,8 +451,13 @@ __device__ __forceinline__ void net313_body(const Net313Pair& pr) {
             v = acc[m][b][r] * dmul[m][b][r];
           } else {
             const float z = acc[m][b][r] + a.b1[o];
-            v = swish_fast_f(z, sp1);
-            if constexpr (MODE == MODE_SAVE || MODE == MODE_EVALSAVE) dv[r] = swish_fast_d(z, sp1);
+            if constexpr (ACTK == 0) {
+              v = swish_fast_f(z, sp1);
+              if constexpr (MODE == MODE_SAVE || MODE == MODE_EVALSAVE) dv[r] = swish_fast_d(z, sp1);
+            } else {
+              v = fused_act_f(a.act, z);
+              if constexpr (MODE == MODE_SAVE || MODE == MODE_EVALSAVE) dv[r] = fused_act_d(a.act, z);
+            }
           }
           if constexpr (H3) cm[b] = fmaxf(cm[b], fabsf(v));
           t[o * F_BN + b * 32 + li] = v;
@@ -650,14 +656,17 @@ __device__ __forceinline__ void net313_body(const Net313Pair& pr) {
   STAMP(4);
   WSTAMP(8);
   if constexpr (MODE == MODE_SAVE || MODE == MODE_EVALSAVE) {
-    const float sp2 = softplus_f(ldc(a.beta2));
+    const float sp2 = ACTK == 0 ? softplus_f(ldc(a.beta2)) : 0.f;
 #pragma unroll
     for (int m = 0; m < TM; ++m)
 #pragma unroll
       for (int b = 0; b < NB; ++b) {
         float dv[16];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) dv[r] = swish_fast_d(acc[m][b][r] + a.b2[row_of(m, r)], sp2);
+        for (int r = 0; r < 16; ++r) {
+          if constexpr (ACTK == 0) dv[r] = swish_fast_d(acc[m][b][r] + a.b2[row_of(m, r)], sp2);
+          else dv[r] = fused_act_d(a.act, acc[m][b][r] + a.b2[row_of(m, r)]);
+        }
         store_d(a.d2, m, b, dv);
       }
   }
@@ -674,7 +683,7 @@ __device__ __forceinline__ void net313_body(const Net313Pair& pr) {
           load_d(a.d1, m, b, dmul[m][b]);
         }
     }
-    const float sp2 = (MODE != MODE_VJP) ? softplus_f(ldc(a.beta2)) : 0.f;
+    const float sp2 = (MODE != MODE_VJP && ACTK == 0) ? softplus_f(ldc(a.beta2)) : 0.f;
 #pragma unroll
     for (int m = 0; m < TM; ++m)
 #pragma unroll
@@ -683,7 +692,8 @@ __device__ __forceinline__ void net313_body(const Net313Pair& pr) {
         for (int r = 0; r < 16; ++r) {
           const int o = row_of(m, r);
           if constexpr (MODE == MODE_VJP) acc[m][b][r] = acc[m][b][r] * dmul[m][b][r];
-          else acc[m][b][r] = swish_fast_f(acc[m][b][r] + a.b2[o], sp2);
+          else if constexpr (ACTK == 0) acc[m][b][r] = swish_fast_f(acc[m][b][r] + a.b2[o], sp2);
+          else acc[m][b][r] = fused_act_f(a.act, acc[m][b][r] + a.b2[o]);
         }
     if (pr.tbuf) {       // (timing build only: make the stamp wait for the multiplies)
       float s_ = 0.f;
@@ -987,18 +997,18 @@ __device__ __forceinline__ void net313_body(const Net313Pair& pr) {
 #undef WSTAMP
 }
 
-template <int TM, int MODE, int SPL>
+template <int TM, int MODE, int SPL, int ACTK = 0>
 __global__ __launch_bounds__(512) void net313_kernel(Net313Pair pr) {
-  net313_body<TM, MODE, 64, LDS_FULL, SPL>(pr);
+  net313_body<TM, MODE, 64, LDS_FULL, SPL, 8, ACTK>(pr);
 }
 // two workgroups (16 waves) per CU: at most 128 VGPRs
-template <int TM, int MODE, int SPL>
+template <int TM, int MODE, int SPL, int ACTK = 0>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) void net313_kernel_h(Net313Pair pr) {
-  net313_body<TM, MODE, 32, LDS_HALF, SPL>(pr);
+  net313_body<TM, MODE, 32, LDS_HALF, SPL, 8, ACTK>(pr);
 }
-template <int TM, int MODE, int SPL>
+template <int TM, int MODE, int SPL, int ACTK = 0>
 __global__ __launch_bounds__(512) void net313_kernel_w(Net313Pair pr) {
-  net313_body<TM, MODE, 32, LDS_FULL, SPL>(pr);
+  net313_body<TM, MODE, 32, LDS_FULL, SPL, 8, ACTK>(pr);
 }
 enum { V64 = 0, VHALF = 1, VWIDE = 2 };
 
@@ -1102,6 +1112,9 @@ int launch_net313_multi(const Net313Args* args, int nnets, int hid, int mode, hi
   if (layout_nets <= 0) layout_nets = nnets;
   const Net313Args& a0 = args[0];
   if (!net313_supported(hid, a0.C, a0.H, a0.W) || nnets < 1 || nnets > 2) return INF_ERR_UNSUPPORTED;
+  // one instantiation serves both nets of a pair: Swish (betas) and the kind-switch family do not share one
+  // (engine.hip fused_pair keeps such pairs off this launch)
+  if ((args[0].act != 0) != (args[nnets - 1].act != 0)) return INF_ERR_INVALID;
   const int P = a0.H * a0.W;
   // 64-pixel tiles unless the grid would leave CUs idle; then 32-pixel tiles two per CU; the wide
   // variant when neither fits
@@ -1165,28 +1178,38 @@ int launch_net313_multi(const Net313Args* args, int nnets, int hid, int mode, hi
     }
     return INF_OK;
   }
-#define L313S(TM_, MODE_, SPL_)                                                                         \
-  do {                                                                                                  \
-    if (var == V64) hipLaunchKernelGGL((net313_kernel<TM_, MODE_, SPL_>), dim3(nb), dim3(512), 0, s, pr); \
-    else if (var == VHALF) hipLaunchKernelGGL((net313_kernel_h<TM_, MODE_, SPL_>), dim3(nb), dim3(512), 0, s, pr); \
-    else hipLaunchKernelGGL((net313_kernel_w<TM_, MODE_, SPL_>), dim3(nb), dim3(512), 0, s, pr);           \
+  // the forward modes of a net with another fused activation (Net313Args::act) take the ACTK = 1 instantiations; the
+  // VJP reads only the saved derivatives and is shared
+  const bool actk = a0.act != 0;
+#define L313S(TM_, MODE_, SPL_, AK_)                                                                         \
+  do {                                                                                                       \
+    if (var == V64) hipLaunchKernelGGL((net313_kernel<TM_, MODE_, SPL_, AK_>), dim3(nb), dim3(512), 0, s, pr); \
+    else if (var == VHALF)                                                                                   \
+      hipLaunchKernelGGL((net313_kernel_h<TM_, MODE_, SPL_, AK_>), dim3(nb), dim3(512), 0, s, pr);           \
+    else hipLaunchKernelGGL((net313_kernel_w<TM_, MODE_, SPL_, AK_>), dim3(nb), dim3(512), 0, s, pr);        \
   } while (0)
-#define L313(TM_, MODE_, BN_)            \
-  do {                                   \
-    if (h3) L313S(TM_, MODE_, 2);        \
-    else if (split) L313S(TM_, MODE_, 1); \
-    else L313S(TM_, MODE_, 0);           \
+#define L313(TM_, MODE_, AK_)                  \
+  do {                                         \
+    if (h3) L313S(TM_, MODE_, 2, AK_);         \
+    else if (split) L313S(TM_, MODE_, 1, AK_); \
+    else L313S(TM_, MODE_, 0, AK_);            \
   } while (0)
-#define L313M(TM_, BN_)                                \
-  do {                                                 \
-    if (mode == MODE_EVAL) L313(TM_, MODE_EVAL, BN_);  \
-    else if (mode == MODE_SAVE) L313(TM_, MODE_SAVE, BN_); \
-    else if (mode == MODE_EVALSAVE) L313(TM_, MODE_EVALSAVE, BN_); \
-    else L313(TM_, MODE_VJP, BN_);                     \
+#define L313F(TM_, MODE_)            \
+  do {                               \
+    if (actk) L313(TM_, MODE_, 1);   \
+    else L313(TM_, MODE_, 0);        \
   } while (0)
-  if (hid == 512) L313M(2, bn);
-  else L313M(1, bn);
+#define L313M(TM_)                                            \
+  do {                                                        \
+    if (mode == MODE_EVAL) L313F(TM_, MODE_EVAL);             \
+    else if (mode == MODE_SAVE) L313F(TM_, MODE_SAVE);        \
+    else if (mode == MODE_EVALSAVE) L313F(TM_, MODE_EVALSAVE); \
+    else L313(TM_, MODE_VJP, 0);                              \
+  } while (0)
+  if (hid == 512) L313M(2);
+  else L313M(1);
 #undef L313M
+#undef L313F
 #undef L313
 #undef L313S
   INF_CHECK_LAUNCH();

@@ -59,7 +59,7 @@ __device__ __forceinline__ void stage_halo(const Net313Args& a, const HaloGeom& 
     const float* ytap = a.in_taps + (long)g.img * (9 * C) * P;
     const float* mx = a.vmul_x ? a.vmul_x + (long)g.img * C * P : nullptr;
     const float* ep = a.dot_eps ? a.dot_eps + (long)g.img * C * P : nullptr;
-    const float msp = a.vmul_x ? softplus_f(ldc(a.vmul_beta)) : 0.f;
+    const float msp = (a.vmul_x && !a.vmul_act) ? softplus_f(ldc(a.vmul_beta)) : 0.f;
     const float* mxp = mx ? mx : ytap;
     const float* epp = ep ? ep : ytap;
     float* accw = a.acc_w ? a.acc_w + (long)g.img * C * P : nullptr;   // Neumann-vector accumulator
@@ -104,7 +104,7 @@ __device__ __forceinline__ void stage_halo(const Net313Args& a, const HaloGeom& 
           const bool vt = y2 >= 0 && y2 < H && x2 >= 0 && x2 < W;
           v += vt ? tv[u][tp] : 0.f;
         }
-        if (mx) v = v * swish_fast_d(xm[u], msp);
+        if (mx) v = v * (a.vmul_act ? fused_act_d(a.vmul_act, xm[u]) : swish_fast_d(xm[u], msp));
         v = ok ? v : 0.f;
         if (ep && ok == 2) dacc += (double)v * (double)ev[u];
         if (accw && ok == 2) accw[(long)c * P + yy * W + xx] = fmaf(a.acc_coef, v, wv[u]);
@@ -142,6 +142,7 @@ __device__ __forceinline__ void stage_halo(const Net313Args& a, const HaloGeom& 
         if (ok[u]) {
           v = lv[u];
           if (a.pre_beta) v = swish_fast_f(v, pre_sp);
+          else if (a.pre_act) v = fused_act_f(a.pre_act, v);
         }
         hmx = fmaxf(hmx, fabsf(v));
         if (i < vhz) vh[i] = v;

@@ -61,7 +61,8 @@ int net313k_fits(int hid, int C, int H, int W) {
 
 // MODE_VJP: v^T J (epilogues x d2, x d1); MODE_EVAL: the net's forward value (epilogues swish(. + b1 / b2));
 // MODE_SAVE / MODE_EVALSAVE: the forward that writes d1, d2 (SAVE without phase C), as in fused313.hip
-template <int MODE, int CT, int WT>
+// ACTK: 0 Swish, 1 the other fused activations by Net313Args::act (forward modes; fused313.hip net313_body)
+template <int MODE, int CT, int WT, int ACTK = 0>
 __global__ __launch_bounds__(512) void net313k_kernel(Net313Pair pr) {
   constexpr bool VJP = MODE == MODE_VJP;
   // forward modes that also write the activation derivatives d1 = swish'(a1), d2 = swish'(a2) in the 64-pixel kernel's
@@ -217,7 +218,7 @@ __global__ __launch_bounds__(512) void net313k_kernel(Net313Pair pr) {
   const u32x4* A3p = reinterpret_cast<const u32x4*>(a.A3p);
   const int nkt1 = K1pad / 16;
   const int ew = ldc(a.Ah_exp + 1);
-  const float sp1 = VJP ? 0.f : softplus_f(ldc(a.beta1)), sp2 = VJP ? 0.f : softplus_f(ldc(a.beta2));
+  const float sp1 = (VJP || ACTK) ? 0.f : softplus_f(ldc(a.beta1)), sp2 = (VJP || ACTK) ? 0.f : softplus_f(ldc(a.beta2));
 
   // writes this wave's values of one 32-row block (rows kt0 * 16 .. + 31 of the chunk) and column block b
   // into the chunk buffer: accumulator group g holds rows 8g + 4 lh + q, which consumer lane 32 (g & 1) + li
@@ -361,8 +362,13 @@ __global__ __launch_bounds__(512) void net313k_kernel(Net313Pair pr) {
             for (int q = 0; q < 4; ++q) {
               const int row = rbA * 32 + q + 8 * j + 4 * lh;
               const float z = __builtin_amdgcn_ldexpf(ac[g][4 * j + q], eA) + a.b1[row];
-              va[b][4 * j + q] = swish_fast_f(z, sp1);
-              if constexpr (SAVE) dd[q] = swish_fast_d(z, sp1);
+              if constexpr (ACTK == 0) {
+                va[b][4 * j + q] = swish_fast_f(z, sp1);
+                if constexpr (SAVE) dd[q] = swish_fast_d(z, sp1);
+              } else {
+                va[b][4 * j + q] = fused_act_f(a.act, z);
+                if constexpr (SAVE) dd[q] = fused_act_d(a.act, z);
+              }
             }
             if constexpr (SAVE) const_cast<f32x4*>(dptr(a.d1, rbA, b))[j] = dd;
           }
@@ -528,8 +534,13 @@ __global__ __launch_bounds__(512) void net313k_kernel(Net313Pair pr) {
         for (int r = 0; r < 16; ++r) {
           const int row = (2 * wid + m) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
           const float z = __builtin_amdgcn_ldexpf(acc[m][b][r], e) + a.b2[row];
-          acc[m][b][r] = swish_fast_f(z, sp2);
-          if constexpr (SAVE) dd[r] = swish_fast_d(z, sp2);
+          if constexpr (ACTK == 0) {
+            acc[m][b][r] = swish_fast_f(z, sp2);
+            if constexpr (SAVE) dd[r] = swish_fast_d(z, sp2);
+          } else {
+            acc[m][b][r] = fused_act_f(a.act, z);
+            if constexpr (SAVE) dd[r] = fused_act_d(a.act, z);
+          }
         }
         if constexpr (SAVE) {
           f32x4* q = const_cast<f32x4*>(dptr(a.d2, 2 * wid + m, b));
@@ -637,13 +648,22 @@ __global__ __launch_bounds__(512) void net313k_kernel(Net313Pair pr) {
 
 int launch_net313k(const Net313Pair& pr, int mode, unsigned nb, hipStream_t s) {
   if (pr.a[0].A3p == nullptr || pr.a[1].A3p == nullptr) return INF_ERR_UNSUPPORTED;
+  if ((pr.a[0].act != 0) != (pr.a[1].act != 0)) return INF_ERR_INVALID;   // (launch_net313_multi has refused it)
   const int C = pr.a[0].C, W = pr.a[0].W;
-#define K128_GEO(CT_, WT_)                                                                                        \
-  do {                                                                                                            \
-    if (mode == MODE_VJP) hipLaunchKernelGGL((net313k_kernel<MODE_VJP, CT_, WT_>), dim3(nb), dim3(KB_NT), 0, s, pr); \
-    else if (mode == MODE_EVAL) hipLaunchKernelGGL((net313k_kernel<MODE_EVAL, CT_, WT_>), dim3(nb), dim3(KB_NT), 0, s, pr); \
-    else if (mode == MODE_SAVE) hipLaunchKernelGGL((net313k_kernel<MODE_SAVE, CT_, WT_>), dim3(nb), dim3(KB_NT), 0, s, pr); \
-    else hipLaunchKernelGGL((net313k_kernel<MODE_EVALSAVE, CT_, WT_>), dim3(nb), dim3(KB_NT), 0, s, pr);          \
+  const bool actk = pr.a[0].act != 0;   // another fused activation: the forward modes' ACTK = 1 instantiations
+#define K128_L(MODE_, CT_, WT_, AK_) \
+  hipLaunchKernelGGL((net313k_kernel<MODE_, CT_, WT_, AK_>), dim3(nb), dim3(KB_NT), 0, s, pr)
+#define K128_F(MODE_, CT_, WT_)              \
+  do {                                       \
+    if (actk) K128_L(MODE_, CT_, WT_, 1);    \
+    else K128_L(MODE_, CT_, WT_, 0);         \
+  } while (0)
+#define K128_GEO(CT_, WT_)                                      \
+  do {                                                          \
+    if (mode == MODE_VJP) K128_L(MODE_VJP, CT_, WT_, 0);        \
+    else if (mode == MODE_EVAL) K128_F(MODE_EVAL, CT_, WT_);    \
+    else if (mode == MODE_SAVE) K128_F(MODE_SAVE, CT_, WT_);    \
+    else K128_F(MODE_EVALSAVE, CT_, WT_);                       \
   } while (0)
   if (mode != MODE_VJP && mode != MODE_EVAL && mode != MODE_SAVE && mode != MODE_EVALSAVE) return INF_ERR_UNSUPPORTED;
   if (C == 3 && W == 32) K128_GEO(3, 32);            // CIFAR-10 scale 0
@@ -652,6 +672,8 @@ int launch_net313k(const Net313Pair& pr, int mode, unsigned nb, hipStream_t s) {
   else if (C == 12 && W == 128) K128_GEO(12, 128);   // CelebA-HQ 256 scale 1
   else K128_GEO(0, 0);
 #undef K128_GEO
+#undef K128_F
+#undef K128_L
   INF_CHECK_LAUNCH();
   return INF_OK;
 }

@@ -108,6 +108,11 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_f32_kernel(GemmArgs g) {
         if (g.pre_beta) {
           v.x = swish_f(v.x, pre_sp); v.y = swish_f(v.y, pre_sp);
           v.z = swish_f(v.z, pre_sp); v.w = swish_f(v.w, pre_sp);
+        } else if constexpr (EPI == EP_ACT_ANY) {   // (only this epilogue's instantiations carry the switch)
+          if (g.pre_act != ACT_NONE) {
+            v.x = act_any_f(g.pre_act, v.x); v.y = act_any_f(g.pre_act, v.y);
+            v.z = act_any_f(g.pre_act, v.z); v.w = act_any_f(g.pre_act, v.w);
+          }
         }
         rb4[i] = v;
       }
@@ -119,6 +124,9 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_f32_kernel(GemmArgs g) {
         if (colok && k < g.Ktot) {
           v = colbase[(long)k * g.P];
           if (g.pre_beta) v = swish_f(v, pre_sp);
+          else if constexpr (EPI == EP_ACT_ANY) {
+            if (g.pre_act != ACT_NONE) v = act_any_f(g.pre_act, v);
+          }
         }
         rb1[i] = v;
       }
@@ -134,6 +142,9 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_f32_kernel(GemmArgs g) {
           if (yy >= 0 && yy < g.H && xx >= 0 && xx < g.W) {
             v = colbase[(long)c * g.P + yy * g.W + xx];
             if (g.pre_beta) v = swish_f(v, pre_sp);
+            else if constexpr (EPI == EP_ACT_ANY) {
+              if (g.pre_act != ACT_NONE) v = act_any_f(g.pre_act, v);
+            }
           }
         }
         rb1[i] = v;
@@ -312,6 +323,9 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_f32_kernel(GemmArgs g) {
             } else if constexpr (EPI == EP_ACT_SIN) {
               if (g.deriv_out) g.deriv_out[o] = sinact_d(z);
               if (g.write_out) g.out[o] = sinact_f(z);
+            } else if constexpr (EPI == EP_ACT_ANY) {
+              if (g.deriv_out) g.deriv_out[o] = act_any_d(g.act, z);
+              if (g.write_out) g.out[o] = act_any_f(g.act, z);
             } else {
               if (g.deriv_out) g.deriv_out[o] = 1.f;
               if (g.write_out) g.out[o] = z;
@@ -347,6 +361,9 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_f32_kernel(GemmArgs g) {
           } else if constexpr (EPI == EP_ACT_SIN) {
             if (g.deriv_out) g.deriv_out[o] = sinact_d(z);
             if (g.write_out) g.out[o] = sinact_f(z);
+          } else if constexpr (EPI == EP_ACT_ANY) {
+            if (g.deriv_out) g.deriv_out[o] = act_any_d(g.act, z);
+            if (g.write_out) g.out[o] = act_any_f(g.act, z);
           } else {
             if (g.deriv_out) g.deriv_out[o] = 1.f;
             if (g.write_out) g.out[o] = z;
@@ -391,6 +408,7 @@ static int dispatch_cfg(const GemmArgs& g, int bload, int epi, bool vec, hipStre
     case EP_ACT_SWISH: return run<WM, WN, TM, TN, BL, EP_ACT_SWISH, V>(g, s); \
     case EP_ACT_SIN: return run<WM, WN, TM, TN, BL, EP_ACT_SIN, V>(g, s); \
     case EP_ACT_NONE: return run<WM, WN, TM, TN, BL, EP_ACT_NONE, V>(g, s); \
+    case EP_ACT_ANY: return run<WM, WN, TM, TN, BL, EP_ACT_ANY, V>(g, s); \
     case EP_MUL_DERIV: return run<WM, WN, TM, TN, BL, EP_MUL_DERIV, V>(g, s); \
     case EP_BIAS_PRIMAL: return run<WM, WN, TM, TN, BL, EP_BIAS_PRIMAL, V>(g, s); \
     default: return INF_ERR_INVALID;                                     \
@@ -406,7 +424,13 @@ static int dispatch_cfg(const GemmArgs& g, int bload, int epi, bool vec, hipStre
 }
 
 int launch_gemm(const GemmArgs& g, int bload, int epi, hipStream_t s) {
-  if (epi == EP_BIAS_ACT) epi = g.act == ACT_SWISH ? EP_ACT_SWISH : (g.act == ACT_SIN ? EP_ACT_SIN : EP_ACT_NONE);
+  if (epi == EP_BIAS_ACT)
+    epi = g.act == ACT_SWISH ? EP_ACT_SWISH
+                             : (g.act == ACT_SIN ? EP_ACT_SIN : (g.act == ACT_NONE ? EP_ACT_NONE : EP_ACT_ANY));
+  if (!g.pre_beta && g.pre_act == ACT_SWISH) return INF_ERR_INVALID;   // a leading Swish comes with its beta
+  // a parameter-less leading activation is applied by the EP_ACT_ANY instantiations' loader only, so that the Swish /
+  // Sin / plain instantiations keep the registers they had (inf_net_create admits no other combination)
+  if (!g.pre_beta && g.pre_act != ACT_NONE && epi != EP_ACT_ANY) return INF_ERR_UNSUPPORTED;
   if (g.Kpad % 16 != 0 || g.M <= 0 || g.N < 0) return INF_ERR_INVALID;
   const bool vec = (bload == BL_DIRECT) && (g.P % 4 == 0) && (g.N % 4 == 0) && (g.x_sample % 4 == 0) &&
                    ((uintptr_t)g.X % 16 == 0);

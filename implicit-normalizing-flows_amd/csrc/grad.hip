@@ -620,10 +620,17 @@ __global__ void act_apply_kernel(const float* h, const float* beta, float* out, 
   if constexpr (ACT == ACT_SWISH) out[i] = swish_f(h[i], softplus_f(*beta));
   else out[i] = sinact_f(h[i]);
 }
+// the parameter-less kinds by a run-time switch (common.h act_any_f)
+__global__ void act_apply_any_kernel(const float* h, int act, float* out, long n) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  out[i] = act_any_f(act, h[i]);
+}
 int launch_act_apply(const float* h, int act, const float* beta, float* out, long n, hipStream_t s) {
   const dim3 g((unsigned)((n + 255) / 256));
   if (act == ACT_SWISH) hipLaunchKernelGGL(act_apply_kernel<ACT_SWISH>, g, dim3(256), 0, s, h, beta, out, n);
-  else hipLaunchKernelGGL(act_apply_kernel<ACT_SIN>, g, dim3(256), 0, s, h, beta, out, n);
+  else if (act == ACT_SIN) hipLaunchKernelGGL(act_apply_kernel<ACT_SIN>, g, dim3(256), 0, s, h, beta, out, n);
+  else hipLaunchKernelGGL(act_apply_any_kernel, g, dim3(256), 0, s, h, act, out, n);
   INF_CHECK_LAUNCH();
   return INF_OK;
 }

@@ -12,7 +12,9 @@ namespace inf {
 enum BLoad { BL_DIRECT = 0, BL_IM2COL3 = 1 };
 enum Epi { EP_STORE = 0, EP_BIAS = 1, EP_BIAS_ACT = 2, EP_MUL_DERIV = 3, EP_BIAS_PRIMAL = 4,
            // compile-time activation variants of EP_BIAS_ACT (selected by launch_gemm from GemmArgs::act)
-           EP_ACT_SWISH = 5, EP_ACT_SIN = 6, EP_ACT_NONE = 7 };
+           EP_ACT_SWISH = 5, EP_ACT_SIN = 6, EP_ACT_NONE = 7,
+           // one instantiation for the parameter-less activations (ELU .. Zero): wave-uniform switch on GemmArgs::act
+           EP_ACT_ANY = 8 };
 
 struct GemmArgs {
   const float* A;
@@ -33,6 +35,7 @@ struct GemmArgs {
   const float* deriv_in;  // EP_MUL_DERIV multiplier (same indexing as out)
   int n_primal;           // EP_BIAS_PRIMAL: columns n < n_primal get the bias
   int x6;                 // 1: split-bf16 MFMA (both operands split exactly into 3 bf16 pieces, common.h)
+  int pre_act;            // loader applies this parameter-less Act to X (pre_beta null; ACT_NONE: nothing)
 };
 int launch_gemm(const GemmArgs& g, int bload, int epi, hipStream_t s);
 
@@ -54,6 +57,7 @@ struct OutArgs {
   float* out1;
   float* out2;            // OM_RESID (optional): the net output f(z) itself
   const float* pre_beta;  // OM_VJP: multiply by swish'(in1) (preact input derivative)
+  int pre_act;            // OM_VJP, pre_beta null: multiply by this parameter-less Act's derivative at in1 (ACT_NONE: 1)
   double* partial;        // (B, nchunk) per-sample partial sums (OM_RESID: g^2, OM_VJP: v.eps)
   int nchunk;
   int sample_sums;        // OM_RESID, conv nets: one block per sample writes the sample's total to partial[b] (the chunk
@@ -218,6 +222,10 @@ struct Net313Args {
   int tile_order;         // 1: the 128-pixel kernel walks the tiles backwards (series terms alternate; args[0])
   int presplit;           // INF_OPT_FUSED_PRESPLIT: the wide 32-pixel kernel's B operands split once in LDS (args[0])
   int exact_scale;        // INF_OPT_K128_EXACT_SCALE: chunk 1's exact-scale path on every tile (args[0]; tests)
+  // activations other than Swish (0: Swish with the betas above; else ACT_ELU / ACT_SOFTPLUS / ACT_RELU, betas NULL):
+  int act;                // both hidden activations: selects the kernels' "other" instantiations (args[0] decides)
+  int pre_act;            // forward: the leading activation applied to `in` by the halo staging (pre_beta NULL)
+  int vmul_act;           // with vmul_x: v *= act'(vmul_x) (vmul_beta NULL)
 };
 struct Net313Pair {
   Net313Args a[2];

@@ -88,6 +88,7 @@ __global__ __launch_bounds__(OUT_CH) void conv_out_kernel(OutArgs a) {
       default: {  // OM_VJP
         float v = s;
         if (a.pre_beta) v = v * swish_d(a.in1[ei], sp);
+        else if (a.pre_act != ACT_NONE) v = v * act_any_d(a.pre_act, a.in1[ei]);
         a.out0[ei] = v;
         if (a.partial) acc += (double)v * (double)a.in0[ei];
       }
@@ -463,6 +464,7 @@ __global__ __launch_bounds__(256) void fc_out_kernel(OutArgs a, int batch) {
       default: {
         float v = s;
         if (a.pre_beta) v = v * swish_d(a.in1[ei], sp);
+        else if (a.pre_act != ACT_NONE) v = v * act_any_d(a.pre_act, a.in1[ei]);
         a.out0[ei] = v;
         if (a.partial) acc += (double)v * (double)a.in0[ei];
       }
@@ -1653,9 +1655,9 @@ __global__ void fwdmode_act_kernel(float* a, int d_out, int batch, int ntang, in
   } else if (act == ACT_SIN) {
     y = sinact_f(z);
     dz = sinact_d(z);
-  } else {
-    y = z;
-    dz = 1.f;
+  } else {   // the parameter-less kinds (ACT_NONE / ACT_IDENTITY: y = z, dz = 1)
+    y = act_any_f(act, z);
+    dz = act_any_d(act, z);
   }
   row[b] = y;
   for (int j = 1; j <= ntang; ++j) row[(long)j * batch + b] *= dz;

@@ -19,6 +19,7 @@ LIB_PATH = os.path.join(_HERE, 'libinflow.so')
 LIB_PATH = os.environ.get('INFLOW_LIB') or LIB_PATH   # development knob: an alternative build
 
 INF_LAYER_CONV, INF_LAYER_LINEAR, INF_ACT_SWISH, INF_ACT_SIN = 1, 2, 3, 4
+INF_ACT_ELU, INF_ACT_SOFTPLUS, INF_ACT_RELU, INF_ACT_LCUBE, INF_ACT_IDENTITY, INF_ACT_ZERO = 5, 6, 7, 8, 9, 10
 INF_ERR_UNSUPPORTED = 4       # InfStatus (include/inflow.h)
 INF_OPT_FUSED_K128, INF_OPT_EVAL_OVERLAP, INF_OPT_CONVERGENCE, INF_OPT_K128_EXACT_SCALE = 1, 2, 3, 4   # InfNetOption
 INF_OPT_FC_BLOCK, INF_OPT_FC_SERIES, INF_OPT_LINE_SEARCH, INF_OPT_FUSED_PRESPLIT = 5, 6, 7, 8
@@ -276,7 +277,7 @@ class NativeNet:
                 d.ksize = int(w.shape[2]) if kind == INF_LAYER_CONV else 1
                 d.weight, d.bias, d.u, d.v = ptr(w), ptr(m.bias), ptr(m.u), ptr(m.v)
                 d.coeff = float(m.coeff)
-                tensors += [w, m.bias, m.u, m.v]
+                tensors += [t for t in (w, m.bias, m.u, m.v) if t is not None]
             elif kind == INF_ACT_SWISH:
                 d.beta = ptr(m.beta)
                 tensors.append(m.beta)
@@ -307,7 +308,7 @@ class NativeNet:
         out = []
         for kind, m in entries:
             if kind in (INF_LAYER_CONV, INF_LAYER_LINEAR):
-                out += [m.weight, m.bias, m.u, m.v]
+                out += [t for t in (m.weight, m.bias, m.u, m.v) if t is not None]
             elif kind == INF_ACT_SWISH:
                 out.append(m.beta)
         return out
@@ -351,6 +352,7 @@ def net_entries(seq):
     Returns None when the net holds a module the engine does not implement."""
     from ..layers.base import lipschitz_ops as lo
     from ..layers.base import nonlin
+    own = {nonlin.LipschitzCube: INF_ACT_LCUBE, nonlin.Identity: INF_ACT_IDENTITY, nonlin.Zero: INF_ACT_ZERO}
     entries = []
     mods = list(seq.children()) if isinstance(seq, torch.nn.Sequential) else None
     if mods is None:
@@ -361,20 +363,34 @@ def net_entries(seq):
             return None
     for m in mods:
         if isinstance(m, lo.InducedNormConv2d):
-            if tuple(m.stride) != (1, 1) or tuple(m.padding) != (m.kernel_size[0] // 2,) * 2 or m.bias is None:
+            if tuple(m.stride) != (1, 1) or tuple(m.padding) != (m.kernel_size[0] // 2,) * 2:
                 return None
-            entries.append((INF_LAYER_CONV, m))
+            entries.append((INF_LAYER_CONV, m))               # bias may be None (a bias-free layer)
         elif isinstance(m, lo.InducedNormLinear):
-            if m.bias is None:
-                return None
             entries.append((INF_LAYER_LINEAR, m))
         elif isinstance(m, nonlin.Swish):
             entries.append((INF_ACT_SWISH, m))
         elif isinstance(m, nonlin.Sin):
             entries.append((INF_ACT_SIN, m))
+        elif type(m) in _PLAIN_ACTS:
+            kind = _PLAIN_ACTS[type(m)](m)
+            if kind is None:                                  # a non-default alpha / beta / threshold
+                return None
+            entries.append((kind, m))
+        elif type(m) in own:
+            entries.append((own[type(m)], m))
         else:
             return None
     return entries
+
+
+# torch's parameter-less activations, at the parameter values the engine's kernels implement (the defaults, which are
+# what implicit_flow.ACT_FNS constructs); `inplace` does not matter to the engine
+_PLAIN_ACTS = {
+    torch.nn.ELU: lambda m: INF_ACT_ELU if float(m.alpha) == 1.0 else None,
+    torch.nn.Softplus: lambda m: INF_ACT_SOFTPLUS if float(m.beta) == 1.0 and float(m.threshold) == 20.0 else None,
+    torch.nn.ReLU: lambda m: INF_ACT_RELU,
+}
 
 
 class _NativeCache(dict):
@@ -408,7 +424,9 @@ def attach_cache(module):
 
 def _unsupported(module):
     return HipError('net %s is not supported by the MI355X engine (supported: nn.Sequential of InducedNormConv2d '
-                    '(stride 1, k in {1,3}) / InducedNormLinear with Swish / Sin)' % type(module).__name__)
+                    '(stride 1, k in {1,3}) / InducedNormLinear, with or without bias, and the activations Swish, Sin, '
+                    'nn.ELU (alpha 1), nn.Softplus (beta 1, threshold 20), nn.ReLU, LipschitzCube, Identity, Zero; '
+                    'the net must end in a layer, not an activation)' % type(module).__name__)
 
 
 def native_net(module, shape, device):
@@ -505,6 +523,7 @@ def tag_name(tag):
     vec, epi, bload = tag % 10, (tag // 10) % 10, (tag // 100) % 10
     cfg = tag // 1000
     wm, wn, tm, tn = cfg // 1000, (cfg // 100) % 10, (cfg // 10) % 10, cfg % 10
-    epis = {0: 'STORE', 1: 'BIAS', 3: 'MUL_DERIV', 4: 'BIAS_PRIMAL', 5: 'ACT_SWISH', 6: 'ACT_SIN', 7: 'ACT_NONE'}
+    epis = {0: 'STORE', 1: 'BIAS', 3: 'MUL_DERIV', 4: 'BIAS_PRIMAL', 5: 'ACT_SWISH', 6: 'ACT_SIN', 7: 'ACT_NONE',
+            8: 'ACT_ANY'}
     return 'gemm_f32_kernel<%d,%d,%d,%d,%s,%s,%s>' % (wm, wn, tm, tn, ['DIRECT', 'IM2COL3'][bload],
                                                         epis.get(epi, str(epi)), 'true' if vec else 'false')

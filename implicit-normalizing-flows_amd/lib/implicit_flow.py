@@ -4,8 +4,9 @@ Builds the same module tree (``transforms.{scale}.chain.{k}...``) as the referen
 options the image configs use, so reference checkpoints / state dicts load unchanged, and the
 forward threads (x, logpx) through the MI355X-backed layers of ``lib.layers``.
 
-Supported: conv or fc residual nets with InducedNorm layers (vnorms all '2'), Swish / Sin
-activations, preact, ActNorm (2d and fc), LogitTransform init layer, squeeze, factor_out, fc_end.
+Supported: conv or fc residual nets with InducedNorm layers (vnorms all '2', with or without bias), every
+activation of ACT_FNS (Swish, ELU, Softplus and ReLU on the fused 3-1-3 conv kernels, the others on the per-layer
+path), preact, ActNorm (2d and fc), LogitTransform init layer, squeeze, factor_out, fc_end.
 Not provided (outside the density-evaluation hot path): quadratic / InvertibleConv,
 MovingBatchNorm, dropout, learn_p, and the hybrid classification heads.
 """

@@ -122,8 +122,9 @@ class InducedNormLinear(nn.Module):
         self.coeff, self.n_iterations, self.atol, self.rtol = coeff, n_iterations, atol, rtol
         self.domain, self.codomain = domain, codomain
         self.weight = nn.Parameter(torch.empty(out_features, in_features))
-        self.bias = nn.Parameter(torch.empty(out_features)) if bias else None
-        if not bias:
+        if bias:
+            self.bias = nn.Parameter(torch.empty(out_features))
+        else:
             self.register_parameter('bias', None)
         init.kaiming_uniform_(self.weight, a=math.sqrt(5))
         if zero_init:

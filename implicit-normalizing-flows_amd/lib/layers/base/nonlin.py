@@ -1,8 +1,9 @@
 """Activation modules of the implicit-flow nets (reference: lib/layers/base/activations.py).
 
-Swish and Sin are the two the MI355X engine fuses into its GEMM epilogues (gemm.hip EP_ACT_*);
-their ``forward`` here is the plain-tensor definition used when a module is called directly
-(e.g. the ``restore=True`` warm-up), never by the imBlock hot path.
+The MI355X engine implements Swish, Sin, LipschitzCube, Identity and Zero (and torch's nn.ELU, nn.Softplus,
+nn.ReLU at their default parameters) in its GEMM epilogues (gemm.hip EP_ACT_*, csrc/common.h); FullSort and MaxMin
+have no engine form.  The ``forward`` here is the plain-tensor definition used when a module is called directly
+(e.g. the ``restore=True`` warm-up, or the autograd training route), never by the imBlock eval hot path.
 """
 import math
 

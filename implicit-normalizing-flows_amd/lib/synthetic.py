@@ -61,6 +61,17 @@ POWER_EXACT = dict(POWER, exact_trace=True)
 CONFIGS = {'cifar10': CIFAR10, 'cifar10_small': CIFAR10_SMALL, 'celebahq256': CELEBAHQ256,
            'power': POWER, 'toy': TOY, 'power_exact': POWER_EXACT}
 
+# The activation table's other entries (implicit_flow.py ACT_FNS) on the architectures above: the fixtures of
+# tests/golden/make_golden_acts.py.  Only Swish has a parameter, so these state dicts hold no '.beta' keys.
+NEW_ACTS = ('elu', 'softplus', 'relu', 'lcube', 'identity', 'zero')
+for _a in NEW_ACTS:
+    CONFIGS['cifar10_small_' + _a] = dict(CIFAR10_SMALL, act=_a)
+for _a in ('elu', 'softplus', 'relu'):
+    CONFIGS['cifar10_' + _a] = dict(CIFAR10, act=_a)
+CONFIGS['power_elu'] = dict(POWER, act='elu')
+CONFIGS['toy_softplus'] = dict(TOY, act='softplus')
+del _a
+
 
 def _rng(seed, key):
     return np.random.Generator(np.random.PCG64([int(seed), zlib.crc32(key.encode())]))
@@ -82,7 +93,7 @@ def conv_flow_layout(arch):
 
     Returns a list of scales; each scale is a list of (kind, info) in chain order with kind in
     {'logit', 'actnorm', 'imblock', 'squeeze'}.  imblock info holds the (C,H,W) it acts on and
-    its net layer list [('swish',), ('conv', cin, cout, k), ...].
+    its net layer list [(act,), ('conv', cin, cout, k), ...] with act = arch['act'].
     """
     c, h, w = arch['input_size']
     ks = list(map(int, arch['kernels'].split('-')))
@@ -99,12 +110,12 @@ def conv_flow_layout(arch):
             first_block = first and b == 0
             net = []
             if not first_block and arch['preact']:
-                net.append(('swish',))
+                net.append((arch['act'],))
             net.append(('conv', c, arch['idim'], ks[0]))
-            net.append(('swish',))
+            net.append((arch['act'],))
             for k in ks[1:-1]:
                 net.append(('conv', arch['idim'], arch['idim'], k))
-                net.append(('swish',))
+                net.append((arch['act'],))
             net.append(('conv', arch['idim'], c, ks[-1]))
             chain.append(('imblock', dict(shape=(c, h, w), net=net)))
             if arch['actnorm']:

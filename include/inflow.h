@@ -40,18 +40,25 @@ typedef enum InfLayerKind {
   INF_LAYER_CONV = 1,    /* InducedNormConv2d  (mixed_lipschitz.py:149-391), stride 1, pad k//2 */
   INF_LAYER_LINEAR = 2,  /* InducedNormLinear  (mixed_lipschitz.py:12-136) */
   INF_ACT_SWISH = 3,     /* Swish              (activations.py:64-71) */
-  INF_ACT_SIN = 4        /* Sin                (activations.py:7-12) */
+  INF_ACT_SIN = 4,       /* Sin                (activations.py:7-12) */
+  /* the parameter-less rest of the activation table (implicit_flow.py:8-17); beta is NULL for them */
+  INF_ACT_ELU = 5,       /* nn.ELU, alpha = 1:                 a > 0 ? a : expm1(a) */
+  INF_ACT_SOFTPLUS = 6,  /* nn.Softplus, beta = 1, threshold 20: a > 20 ? a : log1p(exp(a)) */
+  INF_ACT_RELU = 7,      /* nn.ReLU */
+  INF_ACT_LCUBE = 8,     /* LipschitzCube      (activations.py): a -+ 2/3 outside (-1, 1), a^3 / 3 inside */
+  INF_ACT_IDENTITY = 9,  /* Identity */
+  INF_ACT_ZERO = 10      /* Zero */
 } InfLayerKind;
 
 typedef struct InfLayerDesc {
   int kind;                 /* InfLayerKind */
   int cin, cout, ksize;     /* conv: (cout, cin, k, k) weight; linear: k = 1 */
   const float* weight;      /* raw (un-normalised) weight, device */
-  const float* bias;        /* (cout) device, or NULL */
+  const float* bias;        /* (cout) device, or NULL: a bias-free layer (the engine keeps a zero vector for it) */
   const float* u;           /* spectral-norm vectors u (codomain) / v (domain), device */
   const float* v;
   float coeff;              /* Lipschitz cap: W_eff = W / max(1, u.(W v) / coeff) */
-  const float* beta;        /* Swish beta (1 float) device */
+  const float* beta;        /* Swish beta (1 float) device; NULL for every other activation */
 } InfLayerDesc;
 
 typedef struct InfNetDesc {
