@@ -1,8 +1,8 @@
 // Lipschitz power iteration on the engine: compute_weight(update=True) of InducedNormConv2d /
-// InducedNormLinear, spectral case (mixed_lipschitz.py:85-124 linear, :276-326 1x1, :328-386 kxk):
+// InducedNormLinear (mixed_lipschitz.py:85-124 linear, :276-326 1x1, :328-386 kxk):
 //
-//   repeat up to max_iters:  u <- normalize(W v)      (F.normalize: x / max(|x|_2, 1e-12), in place)
-//                            v <- normalize(W^T u)
+//   repeat up to max_iters:  u <- normalize(W v)      (2 -> 2: F.normalize, x / max(|x|_2, 1e-12), in place;
+//                            v <- normalize(W^T u)     other induced norms: the forms at PINorm below)
 //                            stop when |u - u_old|/sqrt(n_u) < atol + rtol max(u)  and the same for v
 //   sigma = u . (W v)  -> scale
 //
@@ -260,9 +260,220 @@ __global__ __launch_bounds__(256) void pi_sigma_final(const double* part, int np
     if (scale) *scale = (float)v;
   }
 }
-// scratch: 3 * PI_NB doubles
-static void pi_launch_normalize(const float* sv, float* vec, long n, PIState* st, int which, double* scr,
+// ---- induced norms other than 2 -> 2 (mixed_lipschitz.py:406-449).  The normalisation of a vector x depends on
+// the norm p of the space it lives in (v: the domain, u: the codomain); besides x / |x|_2 there are two forms:
+//   PI_ONEHOT  v with domain 1, u with codomain inf: +1 at the lowest index of max |x|, 0 elsewhere (the
+//              reference's projmax_ drops the sign)
+//   PI_POWER   s a^e / (sum (a^e)^np)^inv with a = |x| / max |x|, s = sign(x) (+1 at 0);
+//              v: e = 1/(p-1), np = p, inv = 1/p;  u: e = q-1, np = q/(q-1), inv = (q-1)/q
+//   PI_SIGN    the limits domain = inf / codomain = 1 of PI_POWER: the sign vector, divisor 1
+// The powers run in fp32 (powf), the sums in fp64 in a fixed order; err / max / the stopping rule are those of
+// pi_normalize.
+enum { PI_L2 = 0, PI_ONEHOT = 1, PI_POWER = 2, PI_SIGN = 3 };
+struct PINorm {
+  int mode;
+  float e, np;
+  double inv;
+};
+static PINorm pi_norm_of(float p, bool is_u) {
+  PINorm nm = {PI_L2, 0.f, 0.f, 0.0};
+  if (p == 0.f || p == 2.f) return nm;
+  const bool inf = std::isinf(p);
+  if (is_u ? inf : p == 1.f) {
+    nm.mode = PI_ONEHOT;
+  } else if (is_u ? p == 1.f : inf) {
+    nm.mode = PI_SIGN;
+  } else {
+    nm.mode = PI_POWER;
+    const double q = (double)p;
+    nm.e = (float)(is_u ? q - 1.0 : 1.0 / (q - 1.0));
+    nm.np = (float)(is_u ? q / (q - 1.0) : q);
+    nm.inv = is_u ? (q - 1.0) / q : 1.0 / q;
+  }
+  return nm;
+}
+
+// (|x|, index) pairs: the larger |x| wins, ties go to the lower index, so the order of combination does not matter
+struct PIAmax {
+  float a;
+  long long i;
+};
+__device__ __forceinline__ PIAmax pi_amax_pick(PIAmax x, PIAmax y) {
+  return (y.a > x.a || (y.a == x.a && y.i < x.i)) ? y : x;
+}
+__device__ PIAmax block_reduce_amax(PIAmax v, float* red_a, long long* red_i) {
+  for (int o = 32; o > 0; o >>= 1) {
+    PIAmax w;
+    w.a = __shfl_xor(v.a, o);
+    w.i = __shfl_xor(v.i, o);
+    v = pi_amax_pick(v, w);
+  }
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  __syncthreads();
+  if (lane == 0) {
+    red_a[wid] = v.a;
+    red_i[wid] = v.i;
+  }
+  __syncthreads();
+  PIAmax m = {red_a[0], red_i[0]};
+  for (int k = 1; k < nw; ++k) m = pi_amax_pick(m, PIAmax{red_a[k], red_i[k]});
+  return m;
+}
+__device__ __forceinline__ float pi_sign(float x) { return x < 0.f ? -1.f : 1.f; }
+
+// err / max of one vector's update and, after v's, the stopping rule (thread 0 only; as pi_normalize's tail)
+__device__ void pi_finish(PIState* st, int which, double e, double mx, long n) {
+  const double err = sqrt(e) / sqrt((double)n);
+  if (which == 0) {
+    st->err_u = err;
+    st->max_u = mx;
+    return;
+  }
+  st->iters += 1;
+  if (st->use_tol) {
+    const double tol_u = (double)st->atol + (double)st->rtol * st->max_u;
+    const double tol_v = (double)st->atol + (double)st->rtol * mx;
+    if (st->err_u < tol_u && err < tol_v) st->done = 1;
+  }
+}
+
+// One workgroup, any form but PI_L2.  PI_POWER overwrites s with s a^e on the way (s is iteration scratch).
+__global__ __launch_bounds__(1024) void pi_normalize_p(float* __restrict__ s, float* vec, long n, PIState* st,
+                                                       int which, PINorm nm) {
+  __shared__ double red[16];
+  __shared__ float red_a[16];
+  __shared__ long long red_i[16];
+  if (st->done) return;
+  PIAmax am = {-1.f, 0x7fffffffffffffffLL};
+  if (nm.mode != PI_SIGN) {
+    for (long i = threadIdx.x; i < n; i += blockDim.x) {
+      const float a = fabsf(s[i]);
+      if (a > am.a) am = PIAmax{a, (long long)i};
+    }
+    am = block_reduce_amax(am, red_a, red_i);
+  }
+  float nrm = 1.f;
+  if (nm.mode == PI_POWER) {
+    double ss = 0.0;
+    for (long i = threadIdx.x; i < n; i += blockDim.x) {
+      const float x = s[i];
+      const float t = powf(fabsf(x) / am.a, nm.e);
+      ss += (double)powf(t, nm.np);
+      s[i] = pi_sign(x) * t;
+    }
+    ss = block_reduce_sum(ss, red);
+    nrm = (float)pow(ss, nm.inv);
+  }
+  double e = 0.0, mx = -INFINITY;
+  for (long i = threadIdx.x; i < n; i += blockDim.x) {
+    const float nv = nm.mode == PI_ONEHOT ? (i == am.i ? 1.f : 0.f) : nm.mode == PI_SIGN ? pi_sign(s[i]) : s[i] / nrm;
+    const double d = (double)nv - (double)vec[i];
+    e += d * d;
+    mx = fmax(mx, (double)nv);
+    vec[i] = nv;
+  }
+  e = block_reduce_sum(e, red);
+  mx = block_reduce_max(mx, red);
+  if (threadIdx.x == 0) pi_finish(st, which, e, mx, n);
+}
+
+// The PI_NB-workgroup form for long vectors:
+//   pi_amax_part  per-workgroup (max |x|, lowest index of it)            (PI_ONEHOT, PI_POWER)
+//   pi_pow_part   every workgroup re-reduces the maxima, overwrites its slice of s with s a^e and writes its
+//                 partial sum of (a^e)^np                                   (PI_POWER)
+//   pi_apply_p    every workgroup re-reduces the partials of the stage before, writes its slice of the new vector
+//                 and its partial |new - old|^2 and max
+//   pi_norm_final as for PI_L2
+__global__ __launch_bounds__(256) void pi_amax_part(const float* __restrict__ s, long n, const PIState* st,
+                                                    double* part_a, double* part_i) {
+  __shared__ float red_a[16];
+  __shared__ long long red_i[16];
+  if (st->done) return;
+  PIAmax am = {-1.f, 0x7fffffffffffffffLL};
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const float a = fabsf(s[i]);
+    if (a > am.a) am = PIAmax{a, (long long)i};
+  }
+  am = block_reduce_amax(am, red_a, red_i);
+  if (threadIdx.x == 0) {
+    part_a[blockIdx.x] = (double)am.a;
+    part_i[blockIdx.x] = __longlong_as_double(am.i);
+  }
+}
+// the (max, index) over the PI_NB partials (blockDim.x >= PI_NB)
+__device__ PIAmax pi_amax_of_parts(const double* part_a, const double* part_i, int nparts, float* red_a,
+                                   long long* red_i) {
+  PIAmax am = {-1.f, 0x7fffffffffffffffLL};
+  if ((int)threadIdx.x < nparts) am = PIAmax{(float)part_a[threadIdx.x], __double_as_longlong(part_i[threadIdx.x])};
+  return block_reduce_amax(am, red_a, red_i);
+}
+__global__ __launch_bounds__(256) void pi_pow_part(float* __restrict__ s, long n, const PIState* st, PINorm nm,
+                                                   const double* part_a, const double* part_i, double* part_s) {
+  __shared__ double red[16];
+  __shared__ float red_a[16];
+  __shared__ long long red_i[16];
+  if (st->done) return;
+  const PIAmax am = pi_amax_of_parts(part_a, part_i, gridDim.x, red_a, red_i);
+  double ss = 0.0;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const float x = s[i];
+    const float t = powf(fabsf(x) / am.a, nm.e);
+    ss += (double)powf(t, nm.np);
+    s[i] = pi_sign(x) * t;
+  }
+  ss = block_reduce_sum(ss, red);
+  if (threadIdx.x == 0) part_s[blockIdx.x] = ss;
+}
+// in: part_a / part_i (PI_ONEHOT) or part_s (PI_POWER); out: part_e / part_m, which no workgroup reads here
+__global__ __launch_bounds__(256) void pi_apply_p(const float* __restrict__ s, float* vec, long n, const PIState* st,
+                                                  PINorm nm, const double* part_a, const double* part_i,
+                                                  const double* part_s, double* part_e, double* part_m) {
+  __shared__ double red[16];
+  __shared__ float red_a[16];
+  __shared__ long long red_i[16];
+  if (st->done) return;
+  long long hot = -1;
+  float nrm = 1.f;
+  if (nm.mode == PI_ONEHOT) {
+    hot = pi_amax_of_parts(part_a, part_i, gridDim.x, red_a, red_i).i;
+  } else if (nm.mode == PI_POWER) {
+    double ss = threadIdx.x < gridDim.x ? part_s[threadIdx.x] : 0.0;
+    ss = block_reduce_sum(ss, red);
+    nrm = (float)pow(ss, nm.inv);
+  }
+  double e = 0.0, mx = -INFINITY;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const float nv = nm.mode == PI_ONEHOT ? (i == hot ? 1.f : 0.f) : nm.mode == PI_SIGN ? pi_sign(s[i]) : s[i] / nrm;
+    const double d = (double)nv - (double)vec[i];
+    e += d * d;
+    mx = fmax(mx, (double)nv);
+    vec[i] = nv;
+  }
+  e = block_reduce_sum(e, red);
+  mx = block_reduce_max(mx, red);
+  if (threadIdx.x == 0) {
+    part_e[blockIdx.x] = e;
+    part_m[blockIdx.x] = mx;
+  }
+}
+
+// scratch: PI_SCR doubles = [0, NB) |x|^2 partials or maxima, [NB, 2NB) err partials, [2NB, 3NB) max partials,
+// [3NB, 4NB) argmax indices, [4NB, 5NB) power sums
+constexpr int PI_SCR = 5 * PI_NB;
+static void pi_launch_normalize(float* sv, float* vec, long n, PIState* st, int which, const PINorm& nm, double* scr,
                                 hipStream_t s) {
+  if (nm.mode != PI_L2) {
+    if (n < PI_MULTI_MIN) {
+      hipLaunchKernelGGL(pi_normalize_p, dim3(1), dim3(1024), 0, s, sv, vec, n, st, which, nm);
+      return;
+    }
+    double *pa = scr, *pe = scr + PI_NB, *pm = scr + 2 * PI_NB, *pidx = scr + 3 * PI_NB, *ps = scr + 4 * PI_NB;
+    if (nm.mode != PI_SIGN) hipLaunchKernelGGL(pi_amax_part, dim3(PI_NB), dim3(256), 0, s, sv, n, st, pa, pidx);
+    if (nm.mode == PI_POWER) hipLaunchKernelGGL(pi_pow_part, dim3(PI_NB), dim3(256), 0, s, sv, n, st, nm, pa, pidx, ps);
+    hipLaunchKernelGGL(pi_apply_p, dim3(PI_NB), dim3(256), 0, s, sv, vec, n, st, nm, pa, pidx, ps, pe, pm);
+    hipLaunchKernelGGL(pi_norm_final, dim3(1), dim3(256), 0, s, n, PI_NB, st, pe, pm, which);
+    return;
+  }
   if (n < PI_MULTI_MIN) {
     hipLaunchKernelGGL(pi_normalize, dim3(1), dim3(1024), 0, s, sv, vec, n, st, which);
     return;
@@ -318,7 +529,78 @@ static int pi_valid(const InfPowerIterDesc* d) {
   } else if (d->kind != INF_LAYER_LINEAR) {
     return 0;
   }
+  // induced norms: 0 stands for 2 (a zero-initialised descriptor of an older caller), INFINITY for inf
+  for (const float p : {d->domain, d->codomain})
+    if (!(p == 0.f || p >= 1.f)) return 0;   // NaN fails both
   return 1;
+}
+
+// The reference's 1x1 conv leaves a stored buffer untouched where its normalisation acts on a temporary
+// (mixed_lipschitz.py:311-315): v for domain 1, u for codomain inf.  Such a vector is iterated on a copy in the
+// workspace and not copied back; sigma still comes from the iterated vectors.
+static bool pi_stale_u(const InfPowerIterDesc* d) {
+  return d->kind == INF_LAYER_CONV && d->ksize == 1 && std::isinf(d->codomain);
+}
+static bool pi_stale_v(const InfPowerIterDesc* d) {
+  return d->kind == INF_LAYER_CONV && d->ksize == 1 && d->domain == 1.f;
+}
+static size_t pi_align(size_t b) { return (b + 255) / 256 * 256; }
+// after the state(s): W v and W^T u, the reduction scratch, then the copies of the buffers that stay stale
+static size_t pi_layer_bytes(const InfPowerIterDesc* d) {
+  const PIOp op = pi_op(d);
+  const size_t nu = (size_t)pi_nu(op), nv = (size_t)pi_nv(op);
+  return pi_align((nu + nv) * sizeof(float)) + pi_align(PI_SCR * sizeof(double)) +
+         (pi_stale_u(d) ? pi_align(nu * sizeof(float)) : 0) + (pi_stale_v(d) ? pi_align(nv * sizeof(float)) : 0);
+}
+
+struct PILayer {
+  PIOp op;
+  long nu, nv;
+  PINorm nmu, nmv;
+  float *us, *vs;   // W v, W^T u
+  float *u, *v;     // the iterated vectors: the module's buffers, or workspace copies of them
+  double* scr;
+};
+// carve one layer's workspace (pi_layer_bytes) and queue the copies of the buffers that stay stale
+static int pi_layer_setup(const InfPowerIterDesc* d, char* cur, PILayer* l, hipStream_t s) {
+  l->op = pi_op(d);
+  l->nu = pi_nu(l->op);
+  l->nv = pi_nv(l->op);
+  l->nmu = pi_norm_of(d->codomain, true);
+  l->nmv = pi_norm_of(d->domain, false);
+  l->us = reinterpret_cast<float*>(cur);
+  l->vs = l->us + l->nu;
+  cur += pi_align((size_t)(l->nu + l->nv) * sizeof(float));
+  l->scr = reinterpret_cast<double*>(cur);
+  cur += pi_align(PI_SCR * sizeof(double));
+  l->u = d->u;
+  l->v = d->v;
+  if (pi_stale_u(d)) {
+    l->u = reinterpret_cast<float*>(cur);
+    cur += pi_align((size_t)l->nu * sizeof(float));
+    INF_HIP(hipMemcpyAsync(l->u, d->u, (size_t)l->nu * sizeof(float), hipMemcpyDeviceToDevice, s));
+  }
+  if (pi_stale_v(d)) {
+    l->v = reinterpret_cast<float*>(cur);
+    INF_HIP(hipMemcpyAsync(l->v, d->v, (size_t)l->nv * sizeof(float), hipMemcpyDeviceToDevice, s));
+  }
+  return INF_OK;
+}
+static void pi_launch_iteration(const PILayer& l, PIState* st, hipStream_t s) {
+  pi_launch_w(l.op, l.v, l.us, st, s);
+  pi_launch_normalize(l.us, l.u, l.nu, st, 0, l.nmu, l.scr, s);
+  pi_launch_wt(l.op, l.u, l.vs, st, s);
+  pi_launch_normalize(l.vs, l.v, l.nv, st, 1, l.nmv, l.scr, s);
+}
+// sigma = u . (W v)   (mixed_lipschitz.py:126,317,378-380)
+static void pi_launch_sigma(const PILayer& l, PIState* st, float* scale, hipStream_t s) {
+  pi_launch_w(l.op, l.v, l.us, nullptr, s);
+  if (l.nu < PI_MULTI_MIN) {
+    hipLaunchKernelGGL(pi_sigma, dim3(1), dim3(1024), 0, s, l.u, l.us, l.nu, st, scale);
+  } else {
+    hipLaunchKernelGGL(pi_dot_part, dim3(PI_NB), dim3(256), 0, s, l.u, l.us, l.nu, nullptr, l.scr);
+    hipLaunchKernelGGL(pi_sigma_final, dim3(1), dim3(256), 0, s, l.scr, PI_NB, st, scale);
+  }
 }
 
 }  // namespace inf
@@ -329,8 +611,7 @@ extern "C" {
 
 size_t inf_power_iteration_workspace_bytes(const InfPowerIterDesc* d) {
   if (!pi_valid(d)) return 0;
-  const PIOp op = pi_op(d);
-  return 256 + (size_t)(pi_nu(op) + pi_nv(op)) * sizeof(float) + 256 + 3 * PI_NB * sizeof(double);
+  return 256 + pi_layer_bytes(d);
 }
 
 int inf_power_iteration(const InfPowerIterDesc* d, int max_iters, int use_tol, float atol, float rtol,
@@ -338,13 +619,10 @@ int inf_power_iteration(const InfPowerIterDesc* d, int max_iters, int use_tol, f
   if (!pi_valid(d) || max_iters < 0) return INF_ERR_INVALID;
   if (!ws || ws_bytes < inf_power_iteration_workspace_bytes(d)) return INF_ERR_WORKSPACE;
   hipStream_t s = (hipStream_t)stream;
-  const PIOp op = pi_op(d);
-  const long nu = pi_nu(op), nv = pi_nv(op);
   char* base = reinterpret_cast<char*>(ws);
   PIState* st = reinterpret_cast<PIState*>(base);
-  float* us = reinterpret_cast<float*>(base + 256);
-  float* vs = us + nu;
-  double* scr = reinterpret_cast<double*>(base + 256 + (((size_t)(nu + nv) * sizeof(float) + 255) / 256) * 256);
+  PILayer l;
+  INF_TRY(pi_layer_setup(d, base + 256, &l, s));
   PIState h;
   memset(&h, 0, sizeof(h));
   hipLaunchKernelGGL(pi_init, dim3(1), dim3(1), 0, s, st, use_tol ? 1 : 0, atol, rtol);
@@ -353,12 +631,7 @@ int inf_power_iteration(const InfPowerIterDesc* d, int max_iters, int use_tol, f
   int done_iters = 0, chunk = use_tol ? 2 : max_iters;
   while (done_iters < max_iters) {
     const int n = std::min(chunk, max_iters - done_iters);
-    for (int k = 0; k < n; ++k) {
-      pi_launch_w(op, d->v, us, st, s);
-      pi_launch_normalize(us, d->u, nu, st, 0, scr, s);
-      pi_launch_wt(op, d->u, vs, st, s);
-      pi_launch_normalize(vs, d->v, nv, st, 1, scr, s);
-    }
+    for (int k = 0; k < n; ++k) pi_launch_iteration(l, st, s);
     INF_CHECK_LAUNCH();
     done_iters += n;
     chunk = std::min(2 * chunk, 8);
@@ -367,14 +640,7 @@ int inf_power_iteration(const InfPowerIterDesc* d, int max_iters, int use_tol, f
     INF_HIP(hipStreamSynchronize(s));
     if (h.done) break;
   }
-  // sigma = u . (W v)   (mixed_lipschitz.py:126,317,378-380)
-  pi_launch_w(op, d->v, us, nullptr, s);
-  if (nu < PI_MULTI_MIN) {
-    hipLaunchKernelGGL(pi_sigma, dim3(1), dim3(1024), 0, s, d->u, us, nu, st, d->scale);
-  } else {
-    hipLaunchKernelGGL(pi_dot_part, dim3(PI_NB), dim3(256), 0, s, d->u, us, nu, nullptr, scr);
-    hipLaunchKernelGGL(pi_sigma_final, dim3(1), dim3(256), 0, s, scr, PI_NB, st, d->scale);
-  }
+  pi_launch_sigma(l, st, d->scale, s);
   INF_CHECK_LAUNCH();
   // the count needs no further readback: with the tolerance test the last flag read came after every
   // iteration kernel; without it every iteration runs
@@ -385,11 +651,6 @@ int inf_power_iteration(const InfPowerIterDesc* d, int max_iters, int use_tol, f
 // ---- many layers at once (update_lipschitz, train_img.py:786-792): the same per-layer iterations and
 // stopping rule, but every unfinished layer's chunk is queued before ONE read-back of all the layers' flags,
 // so the host waits once per chunk (<= 5 times for 30 iterations) instead of once per chunk per layer.
-static size_t pi_layer_bytes(const InfPowerIterDesc* d) {
-  const PIOp op = pi_op(d);
-  return (((size_t)(pi_nu(op) + pi_nv(op)) * sizeof(float) + 255) / 256) * 256 + 3 * PI_NB * sizeof(double) + 256;
-}
-
 size_t inf_power_iteration_batch_workspace_bytes(const InfPowerIterDesc* descs, int n) {
   if (!descs || n <= 0) return 0;
   size_t b = ((sizeof(PIState) * (size_t)n + 255) / 256) * 256;
@@ -410,21 +671,9 @@ int inf_power_iteration_batch(const InfPowerIterDesc* descs, int n, int max_iter
   char* base = reinterpret_cast<char*>(ws);
   PIState* states = reinterpret_cast<PIState*>(base);
   char* cur = base + ((sizeof(PIState) * (size_t)n + 255) / 256) * 256;
-  struct Layer {
-    PIOp op;
-    long nu, nv;
-    float *us, *vs;
-    double* scr;
-  };
-  std::vector<Layer> L(n);
+  std::vector<PILayer> L(n);
   for (int i = 0; i < n; ++i) {
-    Layer& l = L[i];
-    l.op = pi_op(&descs[i]);
-    l.nu = pi_nu(l.op);
-    l.nv = pi_nv(l.op);
-    l.us = reinterpret_cast<float*>(cur);
-    l.vs = l.us + l.nu;
-    l.scr = reinterpret_cast<double*>(cur + (((size_t)(l.nu + l.nv) * sizeof(float) + 255) / 256) * 256);
+    INF_TRY(pi_layer_setup(&descs[i], cur, &L[i], s));
     cur += pi_layer_bytes(&descs[i]);
     hipLaunchKernelGGL(pi_init, dim3(1), dim3(1), 0, s, states + i, use_tol ? 1 : 0, atol, rtol);
   }
@@ -436,13 +685,7 @@ int inf_power_iteration_batch(const InfPowerIterDesc* descs, int n, int max_iter
     const int c = std::min(chunk, max_iters - done_iters);
     for (int i = 0; i < n; ++i) {
       if (!live[i]) continue;
-      const InfPowerIterDesc& d = descs[i];
-      for (int k = 0; k < c; ++k) {
-        pi_launch_w(L[i].op, d.v, L[i].us, states + i, s);
-        pi_launch_normalize(L[i].us, d.u, L[i].nu, states + i, 0, L[i].scr, s);
-        pi_launch_wt(L[i].op, d.u, L[i].vs, states + i, s);
-        pi_launch_normalize(L[i].vs, d.v, L[i].nv, states + i, 1, L[i].scr, s);
-      }
+      for (int k = 0; k < c; ++k) pi_launch_iteration(L[i], states + i, s);
     }
     INF_CHECK_LAUNCH();
     done_iters += c;
@@ -457,16 +700,7 @@ int inf_power_iteration_batch(const InfPowerIterDesc* descs, int n, int max_iter
     }
     if (!any) break;
   }
-  for (int i = 0; i < n; ++i) {      // sigma = u . (W v)
-    const InfPowerIterDesc& d = descs[i];
-    pi_launch_w(L[i].op, d.v, L[i].us, nullptr, s);
-    if (L[i].nu < PI_MULTI_MIN) {
-      hipLaunchKernelGGL(pi_sigma, dim3(1), dim3(1024), 0, s, d.u, L[i].us, L[i].nu, states + i, d.scale);
-    } else {
-      hipLaunchKernelGGL(pi_dot_part, dim3(PI_NB), dim3(256), 0, s, d.u, L[i].us, L[i].nu, nullptr, L[i].scr);
-      hipLaunchKernelGGL(pi_sigma_final, dim3(1), dim3(256), 0, s, L[i].scr, PI_NB, states + i, d.scale);
-    }
-  }
+  for (int i = 0; i < n; ++i) pi_launch_sigma(L[i], states + i, descs[i].scale, s);
   INF_CHECK_LAUNCH();
   if (iters_used)
     for (int i = 0; i < n; ++i) iters_used[i] = use_tol ? h[i].iters : max_iters;

@@ -30,7 +30,8 @@ CONVERGENCE = {'global': INF_CONV_GLOBAL, 'per_sample': INF_CONV_PER_SAMPLE}
 class PowerIterDesc(ctypes.Structure):
     _fields_ = [('kind', ctypes.c_int), ('cin', ctypes.c_int), ('cout', ctypes.c_int), ('ksize', ctypes.c_int),
                 ('height', ctypes.c_int), ('width', ctypes.c_int), ('weight', ctypes.c_void_p),
-                ('u', ctypes.c_void_p), ('v', ctypes.c_void_p), ('scale', ctypes.c_void_p)]
+                ('u', ctypes.c_void_p), ('v', ctypes.c_void_p), ('scale', ctypes.c_void_p),
+                ('domain', ctypes.c_float), ('codomain', ctypes.c_float)]      # 0 stands for 2, inf for the max norm
 
 
 class NetGrads(ctypes.Structure):

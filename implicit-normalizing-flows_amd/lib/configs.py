@@ -3,7 +3,7 @@ reference constructors: train_img.py:411-444 (ImplicitFlow), train_tabular.py:29
 train_toy.py:146-171,224-242 (SequentialFlow of imBlocks)."""
 import torch
 
-from . import layers
+from . import layers, synthetic
 from .implicit_flow import ACT_FNS, ImplicitFlow
 from .layers import base as base_layers
 
@@ -14,11 +14,13 @@ def build_flow(arch, batch=64):
         return ImplicitFlow(
             (batch, c, h, w), n_blocks=arch['n_blocks'], intermediate_dim=arch['idim'], factor_out=False,
             init_layer=layers.LogitTransform(arch['init_alpha']), actnorm=arch['actnorm'], fc=False,
-            coeff=arch['coeff'], vnorms='2222', sn_atol=1e-3, sn_rtol=1e-3, n_power_series=None,
+            coeff=arch['coeff'], vnorms=arch.get('vnorms', '2222'), sn_atol=1e-3, sn_rtol=1e-3, n_power_series=None,
             n_dist=arch['n_dist'], n_samples=1, kernels=arch['kernels'], activation_fn=arch['act'], fc_end=False,
             n_exact_terms=arch['n_exact_terms'], preact=arch['preact'], neumann_grad=True, grad_in_forward=True)
     d = arch['d']
     dims = [d] + list(arch['dims']) + [d]
+
+    norms = synthetic.layer_norms(arch) or [(2, 2)] * (len(dims) - 1)      # train_tabular.py:283-295
 
     def build_nnet():
         mods = []
@@ -26,7 +28,7 @@ def build_flow(arch, batch=64):
             if i > 0:
                 mods.append(ACT_FNS[arch['act']](False))
             mods.append(base_layers.get_linear(a, b, coeff=arch['coeff'], n_iterations=None, atol=1e-3, rtol=1e-3,
-                                               domain=2, codomain=2, zero_init=(b == d)))
+                                               domain=norms[i][0], codomain=norms[i][1], zero_init=(b == d)))
         return torch.nn.Sequential(*mods)
 
     blocks = [layers.imBlock(build_nnet(), build_nnet(), n_dist=arch['n_dist'], n_power_series=None,

@@ -72,6 +72,58 @@ CONFIGS['power_elu'] = dict(POWER, act='elu')
 CONFIGS['toy_softplus'] = dict(TOY, act='softplus')
 del _a
 
+# Mixed induced norms (--vnorms): layer i of every net is bounded in the l_p[i] -> l_p[i+1] norm, 'f' standing for
+# inf.  An arch without the key is all-2.  '13f1' gives 1 -> 3, 3 -> inf and inf -> 1: every normalisation form of
+# csrc/power.hip (one-hot v, power u and v, one-hot u on the 1x1 conv, both sign vectors) on layers that the
+# reference's factories build as InducedNorm layers (lipschitz.py:510-531; '122f' would give its closed-form
+# LopConv2d, which is not provided).  The fixtures of tests/golden/make_golden_vnorms.py.
+CONFIGS['cifar10_small_13f1'] = dict(CIFAR10_SMALL, vnorms='13f1')
+CONFIGS['cifar10_13f1'] = dict(CIFAR10, vnorms='13f1')
+CONFIGS['fc_2332'] = dict(POWER, dims=[32, 32], n_blocks=4, vnorms='2332')
+
+
+# Layers of the mixed-norm power-iteration fixtures (make_golden_vnorms.py): the smallest shapes that reach every
+# normalisation path of csrc/power.hip.  (name, kind, cin, cout, k, hw, [(domain, codomain), ...]); the first pair
+# of each also runs in tolerance mode.
+_INF = float('inf')
+VNORM_LAYERS = [
+    ('lin7x5', 'linear', 5, 7, 1, None, [(1, 2), (2, _INF), (1, _INF), (3, 3), (_INF, 1), (2, 5)]),       # < one wave
+    ('lin130x70', 'linear', 70, 130, 1, None, [(1, 2), (2, _INF), (1, _INF), (3, 3), (_INF, 1), (2, 5)]),
+    ('conv1', 'conv', 3, 5, 1, (4, 4), [(1, _INF), (1, 2), (2, _INF)]),                  # the stale-buffer rule
+    ('conv3_6x5', 'conv', 3, 5, 3, (6, 5), [(1, 2), (2, _INF), (3, 3), (_INF, 1)]),
+    # nu = 73728 (thread-per-output apply), nv = 18432 (wave-per-output apply), both >= PI_MULTI_MIN
+    ('conv3_96', 'conv', 2, 8, 3, (96, 96), [(1, 2), (2, _INF), (3, 3)]),
+]
+VNORM_SAMPLE = 4096      # vectors longer than this are stored as a seeded sample + vec_summary
+
+
+def vnorm_layer_inputs(name, seed):
+    """(W, u0, v0) of a VNORM_LAYERS entry: kaiming-uniform-like W x 3 (sigma well above 1) and N(0, 1) start vectors
+    (the iteration normalises them on its first step), float32, keyed numpy PCG64."""
+    _, kind, cin, cout, k, hw, _ = next(l for l in VNORM_LAYERS if l[0] == name)
+    rng = _rng(seed, 'vnorm.' + name)
+    bound = 3.0 / np.sqrt(cin * k * k)
+    shape = (cout, cin) if kind == 'linear' else (cout, cin, k, k)
+    W = rng.uniform(-bound, bound, size=shape).astype(np.float32)
+    P = 1 if (kind == 'linear' or k == 1) else hw[0] * hw[1]
+    u0 = rng.standard_normal(cout * P).astype(np.float32)
+    v0 = rng.standard_normal(cin * P).astype(np.float32)
+    return _t(W), _t(u0), _t(v0)
+
+
+def vnorm_sample_index(name, n):
+    """Seeded positions of the stored sample of a long vector."""
+    return np.sort(_rng(11, 'vnorm.idx.' + name).choice(n, VNORM_SAMPLE, replace=False))
+
+
+def layer_norms(arch):
+    """[(domain, codomain)] per weight layer of a net (implicit_flow.py:292-299, train_tabular.py:283-295), or None
+    for an arch without 'vnorms'."""
+    if arch.get('vnorms') is None:
+        return None
+    ps = [float('inf') if c == 'f' else float(c) for c in arch['vnorms']]
+    return list(zip(ps[:-1], ps[1:]))
+
 
 def _rng(seed, key):
     return np.random.Generator(np.random.PCG64([int(seed), zlib.crc32(key.encode())]))
@@ -143,33 +195,54 @@ def fc_flow_layout(arch):
 
 
 # ---------------------------------------------------------------------------------------
-# Power iteration (float64) for the InducedNorm u/v buffers (domain = codomain = 2).
+# Power iteration (float64) for the InducedNorm u/v buffers; norms = (domain, codomain), None for 2 -> 2.
 # ---------------------------------------------------------------------------------------
 
-def _power_conv(W, hw, k, rng, iters):
+def _normalize(x, p, is_u):
+    """normalize_u (codomain p) / normalize_v (domain p) of mixed_lipschitz.py:414-444 on a float64 array, p != 2."""
+    if p == (float('inf') if is_u else 1.0):            # one-hot, +1 whatever the sign
+        out = np.zeros_like(x)
+        out[np.argmax(np.abs(x))] = 1.0
+        return out
+    sign = np.where(x < 0, -1.0, 1.0)
+    if p == (1.0 if is_u else float('inf')):            # the limit of the power form: the sign vector
+        return sign
+    a = np.abs(x) / np.abs(x).max()
+    a = a ** ((p - 1) if is_u else 1 / (p - 1))
+    q = p / (p - 1) if is_u else p
+    return sign * a / (a ** q).sum() ** (1 / q)
+
+
+def _power_conv(W, hw, k, rng, iters, norms=None):
     Wt = torch.from_numpy(W.astype(np.float64))
     cin = W.shape[1]
+    dom, cod = norms or (2.0, 2.0)
+    nv = (lambda t: t / t.norm()) if dom == 2 else (lambda t: torch.from_numpy(_normalize(t.numpy(), dom, False)))
+    nu = (lambda t: t / t.norm()) if cod == 2 else (lambda t: torch.from_numpy(_normalize(t.numpy(), cod, True)))
     v = torch.from_numpy(rng.standard_normal(cin * hw[0] * hw[1]))
-    v = v / v.norm()
+    v = nv(v)
     pad = k // 2
     for _ in range(iters):
         u = F.conv2d(v.view(1, cin, *hw), Wt, padding=pad).reshape(-1)
-        u = u / u.norm()
+        u = nu(u)
         v = F.conv_transpose2d(u.view(1, W.shape[0], *hw), Wt, padding=pad).reshape(-1)
-        v = v / v.norm()
+        v = nv(v)
     sigma = float(torch.dot(u, F.conv2d(v.view(1, cin, *hw), Wt, padding=pad).reshape(-1)))
     return u.numpy(), v.numpy(), sigma
 
 
-def _power_mat(W, rng, iters):
+def _power_mat(W, rng, iters, norms=None):
     W = W.astype(np.float64)
+    dom, cod = norms or (2.0, 2.0)
+    nv = (lambda t: t / np.linalg.norm(t)) if dom == 2 else (lambda t: _normalize(t, dom, False))
+    nu = (lambda t: t / np.linalg.norm(t)) if cod == 2 else (lambda t: _normalize(t, cod, True))
     v = rng.standard_normal(W.shape[1])
-    v /= np.linalg.norm(v)
+    v = nv(v)
     for _ in range(iters):
         u = W @ v
-        u /= np.linalg.norm(u)
+        u = nu(u)
         v = W.T @ u
-        v /= np.linalg.norm(v)
+        v = nv(v)
     return u, v, float(u @ (W @ v))
 
 
@@ -177,15 +250,15 @@ def _t(a, dtype=torch.float32):
     return torch.as_tensor(np.asarray(a), dtype=dtype).clone()
 
 
-def _conv_entries(sd, key, cin, cout, k, hw, seed, power_iters):
+def _conv_entries(sd, key, cin, cout, k, hw, seed, power_iters, norms=None):
     rng = _rng(seed, key)
     bound = 1.0 / np.sqrt(cin * k * k)        # kaiming_uniform(a=sqrt(5)) bound (mixed_lipschitz.py:188-193)
     W = rng.uniform(-bound, bound, size=(cout, cin, k, k)).astype(np.float32)
     b = rng.uniform(-bound, bound, size=(cout,)).astype(np.float32)
     if k == 1:
-        u, v, s = _power_mat(W.reshape(cout, cin), rng, power_iters)
+        u, v, s = _power_mat(W.reshape(cout, cin), rng, power_iters, norms)
     else:
-        u, v, s = _power_conv(W, hw, k, rng, power_iters)
+        u, v, s = _power_conv(W, hw, k, rng, power_iters, norms)
     sd[key + '.weight'] = _t(W)
     sd[key + '.bias'] = _t(b)
     sd[key + '.initialized'] = torch.tensor(1)
@@ -195,12 +268,12 @@ def _conv_entries(sd, key, cin, cout, k, hw, seed, power_iters):
     sd[key + '.v'] = _t(v)
 
 
-def _linear_entries(sd, key, fin, fout, seed, power_iters):
+def _linear_entries(sd, key, fin, fout, seed, power_iters, norms=None):
     rng = _rng(seed, key)
     bound = 1.0 / np.sqrt(fin)
     W = rng.uniform(-bound, bound, size=(fout, fin)).astype(np.float32)
     b = rng.uniform(-bound, bound, size=(fout,)).astype(np.float32)
-    u, v, s = _power_mat(W, rng, power_iters)
+    u, v, s = _power_mat(W, rng, power_iters, norms)
     sd[key + '.weight'] = _t(W)
     sd[key + '.bias'] = _t(b)
     sd[key + '.scale'] = torch.tensor(np.float32(s))
@@ -208,13 +281,14 @@ def _linear_entries(sd, key, fin, fout, seed, power_iters):
     sd[key + '.v'] = _t(v)
 
 
-def _net_entries(sd, prefix, net, hw, seed, power_iters):
+def _net_entries(sd, prefix, net, hw, seed, power_iters, norms=None):
+    norms = iter(norms or [None] * len(net))
     for j, layer in enumerate(net):
         key = '%s.%d' % (prefix, j)
         if layer[0] == 'conv':
-            _conv_entries(sd, key, layer[1], layer[2], layer[3], hw, seed, power_iters)
+            _conv_entries(sd, key, layer[1], layer[2], layer[3], hw, seed, power_iters, next(norms))
         elif layer[0] == 'linear':
-            _linear_entries(sd, key, layer[1], layer[2], seed, power_iters)
+            _linear_entries(sd, key, layer[1], layer[2], seed, power_iters, next(norms))
         elif layer[0] == 'swish':
             sd[key + '.beta'] = _t([_rng(seed, key).uniform(0.3, 0.8)])
 
@@ -226,7 +300,7 @@ def _imblock_entries(sd, prefix, info, arch, seed, power_iters):
     sd[prefix + '.last_firmom'] = torch.zeros(1)
     sd[prefix + '.last_secmom'] = torch.zeros(1)
     for net in ('nnet_x', 'nnet_z'):
-        _net_entries(sd, prefix + '.' + net, info['net'], hw, seed, power_iters)
+        _net_entries(sd, prefix + '.' + net, info['net'], hw, seed, power_iters, layer_norms(arch))
     # frozen copies (implicit_block.py:136-141), refreshed from the nets every forward (:228-229)
     for net in ('nnet_x', 'nnet_z'):
         for k in list(sd.keys()):

@@ -332,8 +332,8 @@ int inf_profile_begin(int max_launches);
 int inf_profile_end(InfKernelStat* out, int max_out, int* n_out);
 
 /* ---- Lipschitz power iteration: compute_weight(update=True) of InducedNormConv2d / InducedNormLinear,
- *      spectral (2 -> 2) case (mixed_lipschitz.py:85-124 linear, :276-326 1x1 conv, :328-386 k x k conv;
- *      called by update_lipschitz, train_img.py:786-792) -------------------------------------------- */
+ *      in the induced norm domain -> codomain (mixed_lipschitz.py:85-124 linear, :276-326 1x1 conv, :328-386
+ *      k x k conv, normalisations :406-449; called by update_lipschitz, train_img.py:786-792) ------------ */
 typedef struct InfPowerIterDesc {
   int kind;              /* INF_LAYER_CONV or INF_LAYER_LINEAR */
   int cin, cout, ksize;  /* conv: stride 1, padding ksize/2; linear: ksize ignored */
@@ -342,6 +342,11 @@ typedef struct InfPowerIterDesc {
   float* u;              /* module buffers, updated in place (u <- W v / |W v|, v <- W^T u / |W^T u|) */
   float* v;
   float* scale;          /* receives sigma = u . (W v) (the module's `scale` buffer); may be NULL */
+  float domain, codomain; /* the induced norm l_domain -> l_codomain: a number >= 1, INFINITY for the max norm, or 0,
+                             which stands for 2 (a zero-initialised descriptor gives the spectral norm).  u is
+                             normalised for the codomain, v for the domain (normalize_u / normalize_v).  A 1x1 conv's
+                             stored v is left untouched for domain 1, its stored u for codomain INFINITY, as the
+                             reference leaves them; scale still receives sigma of the iterated vectors. */
 } InfPowerIterDesc;
 size_t inf_power_iteration_workspace_bytes(const InfPowerIterDesc* desc);
 /* Up to max_iters iterations; with use_tol, stop once |du|/sqrt(n_u) < atol + rtol max(u) and the same for
