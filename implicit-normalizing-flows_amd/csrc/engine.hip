@@ -3117,8 +3117,8 @@ int param_grad_core(InfNet* n, const float* x, const float* gout, float* gx, con
 
 extern "C" {
 // Gradient of sum(gout * f(x)) with respect to every parameter of the net (and x): the recompute graph of the training
-// forward (implicit_block.py:226-227) and the first-order terms of any caller.  Conv nets (Swish) and fc nets (Swish /
-// Sin; x, gout, gx in the (B, d) boundary layout).
+// forward (implicit_block.py:226-227) and the first-order terms of any caller.  Conv and fc nets with Swish / Sin
+// (grad_supported); fc nets: x, gout, gx in the (B, d) boundary layout.
 int inf_net_param_grad(InfNet* n, const float* x, const float* gout, float* gx, const InfNetGrads* gr, int B,
                        void* ws, size_t ws_bytes, void* stream) {
   if (!n || !x || !gout || !gr || B <= 0) return INF_ERR_INVALID;

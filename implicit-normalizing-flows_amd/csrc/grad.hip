@@ -402,6 +402,11 @@ __global__ void slab_reduce_kernel(const float* slab, int nsplit, long n, float*
   out[i] = (float)s;
 }
 
+// Profile tags of the weight-gradient forms: the tiled kernels record 800 + 10 TMW + TNW (811, 812, 821, 822); 899 stays
+// with the row-resident form at W = 32, the one the CIFAR-10 training step spends its VALU weight-gradient time in.
+constexpr int WGRAD_TAG_PLAIN = 890, WGRAD_TAG_VALU = 895, WGRAD_TAG_VALU3 = 896, WGRAD_TAG_VALU3R_8 = 897,
+              WGRAD_TAG_VALU3R_16 = 898, WGRAD_TAG_VALU3R_32 = 899;
+
 int launch_wgrad(const WgradArgs& a0, hipStream_t s) {
   WgradArgs a = a0;
   if (a.M <= WGV_MAXM && a.P > 1 && a.W % 8 == 0 && a.P == a.H * a.W && a.g_sample % 4 == 0 &&
@@ -418,20 +423,27 @@ int launch_wgrad(const WgradArgs& a0, hipStream_t s) {
     a.nsplit = nsplit;
     const bool prof = prof_enabled();
     if (prof) prof_begin_launch(s);
-    if (three && a.W == 32)
+    int tag;                                            // one profile tag per form (lib/_hip tag_name)
+    if (three && a.W == 32) {
+      tag = WGRAD_TAG_VALU3R_32;
       hipLaunchKernelGGL(wgrad_valu3r_kernel<32>, dim3(nb, nsplit), dim3(256), 0, s, a);
-    else if (three && a.W == 16)
+    } else if (three && a.W == 16) {
+      tag = WGRAD_TAG_VALU3R_16;
       hipLaunchKernelGGL(wgrad_valu3r_kernel<16>, dim3(nb, nsplit), dim3(256), 0, s, a);
-    else if (three && a.W == 8)
+    } else if (three && a.W == 8) {
+      tag = WGRAD_TAG_VALU3R_8;
       hipLaunchKernelGGL(wgrad_valu3r_kernel<8>, dim3(nb, nsplit), dim3(256), 0, s, a);
-    else if (three)
+    } else if (three) {
+      tag = WGRAD_TAG_VALU3;
       hipLaunchKernelGGL(wgrad_valu3_kernel, dim3(nb, nsplit), dim3(256), 0, s, a);
-    else
+    } else {
+      tag = WGRAD_TAG_VALU;
       hipLaunchKernelGGL(wgrad_valu_kernel, dim3(nb, nsplit), dim3(256), 0, s, a);
+    }
     INF_CHECK_LAUNCH();
     if (prof) {
       const double K = (double)a.B * a.P;
-      prof_end_launch(s, 899, 2.0 * a.M * a.N * K, 4.0 * K * (a.M + (double)a.N / (a.ks * a.ks)));
+      prof_end_launch(s, tag, 2.0 * a.M * a.N * K, 4.0 * K * (a.M + (double)a.N / (a.ks * a.ks)));
     }
     const long n = (long)a.M * a.N;
     hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a.slab, nsplit, n,
@@ -473,8 +485,15 @@ int launch_wgrad(const WgradArgs& a0, hipStream_t s) {
   int nsplit = (int)std::max<long>(1, std::min<long>(Ktot / 256, 1024 / std::max(1, mt * nt)));
   if (nsplit > a.max_split) nsplit = a.max_split;
   a.nsplit = nsplit;   // a 32-pixel chunk may straddle two images: every element computes its own (b, p)
+  const bool prof = prof_enabled();
+  if (prof) prof_begin_launch(s);
   hipLaunchKernelGGL(wgrad_kernel, dim3(mt, nt, nsplit), dim3(256), 0, s, a);
   INF_CHECK_LAUNCH();
+  if (prof) {
+    const double K = (double)Ktot;
+    prof_end_launch(s, WGRAD_TAG_PLAIN, 2.0 * a.M * a.N * K, 4.0 * K * (a.M + (double)a.N / (a.ks * a.ks)),
+                    2.0 * a.M * a.N * K / PEAK_F32_FLOPS_PER_MS);
+  }
   const long n = (long)a.M * a.N;
   hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a.slab, nsplit, n, a.out);
   INF_CHECK_LAUNCH();

@@ -498,6 +498,13 @@ PHASE_TAGS = {
 }
 
 
+# The weight-gradient forms other than the tiled kernels (grad.hip launch_wgrad; the tiled ones are 8<TMW><TNW>)
+WGRAD_TAGS = {
+    890: 'wgrad_kernel', 895: 'wgrad_valu_kernel', 896: 'wgrad_valu3_kernel', 897: 'wgrad_valu3r_kernel<8>',
+    898: 'wgrad_valu3r_kernel<16>', 899: 'wgrad_valu3r_kernel<32>',
+}
+
+
 def tag_name(tag):
     """Human/rocprof-readable name of a kernel tag (see gemm.hip run<> / pointwise.hip)."""
     if tag in PHASE_TAGS:
@@ -514,9 +521,9 @@ def tag_name(tag):
         return 'fcblock_kernel'
     if tag == 620:           # the power series of an fc net pair in one launch (fcblock.hip)
         return 'fcseries_kernel'
-    if tag == 899:
-        return 'wgrad_valu_kernel'
-    if 800 <= tag < 900:     # weight-gradient kernel (grad.hip), 8<TMW><TNW>
+    if tag in WGRAD_TAGS:
+        return WGRAD_TAGS[tag]
+    if 800 <= tag < 900:     # tiled weight-gradient kernel (grad.hip), 8<TMW><TNW>
         return 'wgrad_tiled_kernel<%d,%d>' % ((tag - 800) // 10, tag % 10)
     if tag < 1000:
         modes = {0: 'PLAIN', 1: 'EMBED', 2: 'RESID', 3: 'RECOMP', 4: 'VJP'}

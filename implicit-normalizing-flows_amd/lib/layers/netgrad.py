@@ -9,8 +9,8 @@
                     log|det(I + J)|, :249-260; the exact-trace series, :323-343), ``inf_logdet_grad``
 
 Weight gradients are with respect to the RAW weights (through the Lipschitz normalisation, like
-autograd through ``compute_weight(update=False)``).  Conv nets with Swish activations and fc nets with Swish / Sin;
-other nets return None and the caller keeps autograd.
+autograd through ``compute_weight(update=False)``).  Conv and fc nets with Swish / Sin between layers that all have a
+bias (conv nets may lead with a Swish); other nets return None and the caller keeps autograd.
 """
 import ctypes
 

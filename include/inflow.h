@@ -360,10 +360,12 @@ size_t inf_power_iteration_batch_workspace_bytes(const InfPowerIterDesc* descs, 
 int inf_power_iteration_batch(const InfPowerIterDesc* descs, int n, int max_iters, int use_tol, float atol,
                               float rtol, int* iters_used, void* ws, size_t ws_bytes, void* stream);
 
-/* ---- parameter gradients (training path; conv nets with swish activations) ------------------------
+/* ---- parameter gradients (training path) -----------------------------------------------------------
+ * Conv and fc nets whose layers all have a bias, with Swish or Sin between the layers, nothing after the last one and,
+ * conv nets only, no leading activation or a leading Swish; any other net: INF_ERR_UNSUPPORTED.
  * Device buffers per weight layer l (in order; NULL entries / arrays are skipped): dW[l] the gradient of
  * the RAW weight (through W / max(1, u.(W v) / coeff), mixed_lipschitz.py:378-385), db[l] the bias,
- * dbeta[l] the beta of the swish applied after layer l (NULL for the last layer); dpre_beta the
+ * dbeta[l] the beta of the swish applied after layer l (NULL for the last layer and after a Sin); dpre_beta the
  * preact swish.  Buffers are overwritten. */
 typedef struct InfNetGrads {
   float** dW;
@@ -373,8 +375,7 @@ typedef struct InfNetGrads {
 } InfNetGrads;
 size_t inf_grad_workspace_bytes(InfNet* net, int batch);
 /* d/dtheta sum(gout * nnet(x)) and d/dx (gx may be NULL): the recompute graph's backward
- * (z = f_x(x0) - f_z(z*) + x0, implicit_block.py:226-227).  Conv nets with Swish; fc nets with Swish / Sin (x, gout,
- * gx in the (B, d) boundary layout). */
+ * (z = f_x(x0) - f_z(z*) + x0, implicit_block.py:226-227).  fc nets: x, gout, gx in the (B, d) boundary layout. */
 int inf_net_param_grad(InfNet* net, const float* x, const float* gout, float* gx, const InfNetGrads* grads,
                        int batch, void* ws, size_t ws_bytes, void* stream);
 /* s_b = w_b^T J(x_b) eps_b (w fixed): value[b] (may be NULL) and d/dx, d/dtheta of sum_b s_b -- the
