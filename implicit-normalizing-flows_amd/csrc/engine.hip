@@ -129,6 +129,9 @@ struct InfNet {
   // fused 3-1-3 path (fused313.hip): fragment-major operands for forward (f) and VJP (b)
   bool fused = false;
   int fhid = 0, K1pad = 0, M3 = 0, M3pad = 0;
+  // fused nets: the tile geometry's per-image maxima over the variants a launch may pick (net313_max_tiles,
+  // net313_tile_pixels): tiles, and pixel columns of the tile-indexed d1 / d2 (P on an exact shape, more on a ragged one)
+  int ftiles = 0, fpix = 0;
   float *F1f = nullptr, *F1b = nullptr, *F2f = nullptr, *F2b = nullptr, *F3f = nullptr, *F3b = nullptr;
   // F1f..F3b split into three bf16 planes each (launch_split3), same order as F1f..F3b
   uint16_t* Fs[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -213,7 +216,10 @@ struct Bufs {
   bool sample_sums = false;   // conv residuals write each sample's total into bf.part (the readback slot; broyden_core)
 };
 
-size_t per_sample_hidden(const InfNet* n) { return (size_t)n->hidden_max * (n->fc ? 1 : n->P); }
+// (a fused net's d1 / d2 are in fragment order per tile: hidden x tiles x tile width floats, dead columns included)
+size_t per_sample_hidden(const InfNet* n) {
+  return (size_t)n->hidden_max * (n->fc ? 1 : (n->fused ? std::max(n->P, n->fpix) : n->P));
+}
 
 // layout-aware sizes: E = B * d elements per vector
 // Carves the workspace; returns the bytes required (fits iff result <= cap).  With ws == nullptr it
@@ -225,7 +231,7 @@ size_t carve(const InfNet* n, int B, int T, void* ws, size_t cap, Bufs& b) {
   const size_t Ys = (size_t)B * n->rows_max * (n->fc ? 1 : n->P);
   const int nchunk = n->fc ? 1 : out_nchunk(n->d);
   b.nchunk = nchunk;
-  b.snchunk = n->fused ? std::max(nchunk, n->P / 32) : nchunk;
+  b.snchunk = n->fused ? std::max(nchunk, std::max(n->P / 32, n->ftiles)) : nchunk;
   b.h0 = w.take<float>(Hs);
   b.h1 = w.take<float>(Hs);
   b.Y = w.take<float>(Ys);
@@ -1900,6 +1906,8 @@ int inf_net_create(const InfNetDesc* desc, InfNet** out) {
     if (shape_ok && !(off && off[0] == '1') && net313_supported(n->L[1].cout, n->C, n->H, n->W)) {
       n->fused = true;
       n->fhid = n->L[1].cout;
+      n->ftiles = net313_max_tiles(n->fhid, n->C, n->H, n->W);
+      n->fpix = net313_tile_pixels(n->fhid, n->C, n->H, n->W);
       n->K1pad = round_up(9 * n->C, 16);
       n->M3 = 9 * n->C;
       n->M3pad = round_up(9 * n->C, 32);

@@ -26,6 +26,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 
+#include <algorithm>
 #include <atomic>
 #include <map>
 #include <string>
@@ -120,14 +121,18 @@ __device__ __forceinline__ void net313_body(const Net313Pair& pr) {
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int li = lane & 31, lh = lane >> 5;
   const int P = a.H * a.W;
-  const int tiles_per_img = P / F_BN;
+  const int tiles_per_img = a.tiles;
   const int img = bid / tiles_per_img, tile = bid - img * tiles_per_img;
-  const int p0 = tile * F_BN;
-  // tile geometry: `rows` image rows of `seg` pixels (seg = min(W, 64))
-  const int seg = a.seg, rows = F_BN / seg;
-  const int y0 = p0 / a.W, x0 = p0 - y0 * a.W;
+  // tile geometry: `rows` image rows of `seg` pixels (seg = min(W, F_BN)).  Whole-row tiles (W <= F_BN) start at row
+  // tile * rows and may be ragged: rows * seg < F_BN leaves dead pixel columns, and the last tile of an image may hold
+  // fewer live rows.  Segment tiles (W > F_BN) are exact.
+  const int seg = a.seg, rows = a.rows;
+  const bool whole = a.W <= F_BN;
+  const int y0 = whole ? tile * rows : tile * F_BN / a.W;
+  const int x0 = whole ? 0 : tile * F_BN - y0 * a.W;
   const HaloGeom hg{a.C, a.H, a.W, seg, rows, a.K1pad, img, tile, y0, x0};
   const int CW = hg.CW(), vhz = hg.vhz();
+  const int live = hg.live_cols();                  // pixel columns n < live are the tile's pixels; F_BN when exact
   float* t = smem;                                  // [HID][F_BN] activation tile
   int* koff = reinterpret_cast<int*>(smem + HID * F_BN);   // [K1pad] im2col offsets into vh
   float* vh = smem + HID * F_BN + a.K1pad;          // [C][RH][CW] halo tile + rows*CW zeros
@@ -189,20 +194,24 @@ __device__ __forceinline__ void net313_body(const Net313Pair& pr) {
   put_wave_dot(a, lane, wid, dacc, red);
   fill_koff<NT>(hg, tid, koff);
   // halo-tile offsets of this lane's pixel in each column block
+  // A dead column takes column 0's offset (always live): it reads only LDS the staging wrote and computes a copy of
+  // column 0 that is never stored to the image and enters no trace partial (those are formed by the staging, over
+  // image pixels).  Its values do sit in the tile-indexed d1 / d2 and in its own column's H3 scale.
+  auto pix_of = [&](int n) {
+    const int py = n / seg;
+    return n < live ? py * CW + (n - py * seg) : 0;
+  };
   int pix[NB];
 #pragma unroll
-  for (int b = 0; b < NB; ++b) {
-    const int n = b * 32 + li;
+  for (int b = 0; b < NB; ++b) pix[b] = pix_of(b * 32 + li);
+  // image offset of pixel column n, -1 for a dead column (phase C masks its tap stores with it)
+  auto gp_of = [&](int n) {
     const int py = n / seg;
-    pix[b] = py * CW + (n - py * seg);
-  }
-  // image offset of this lane's pixel in column block b (phase C tasks: b is a runtime index, so arithmetic
-  // rather than a per-block array, which would live in scratch)
-  auto gp_rt = [&](int b) {
-    const int n = b * 32 + li;
-    const int py = n / seg;
-    return (y0 + py) * a.W + x0 + (n - py * seg);
+    return n < live ? (y0 + py) * a.W + x0 + (n - py * seg) : -1;
   };
+  // ... of this lane's pixel in column block b (phase C tasks: b is a runtime index, so arithmetic rather than a
+  // per-block array, which would live in scratch)
+  auto gp_rt = [&](int b) { return gp_of(b * 32 + li); };
   const long plane = (long)img * HID * P;           // sample offset of HID-channel tensors
   const int rbw = wid * TM;                          // this wave's first 32-row block
   auto row_of = [&](int m, int r) { return (rbw + m) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh; };
@@ -333,8 +342,7 @@ __device__ __forceinline__ void net313_body(const Net313Pair& pr) {
         // and column block instead of 8 gathered ds_read_b32 and the split)
         for (int s_ = tid; s_ < nkt * 64 * NB; s_ += NT) {
           const int kt = s_ / (64 * NB), rem = s_ - kt * (64 * NB), b = rem >> 6, ln = rem & 63;
-          const int n = b * 32 + (ln & 31), py = n / seg;
-          const int px_ = py * CW + (n - py * seg);
+          const int px_ = pix_of(b * 32 + (ln & 31));
           const int* kp = koff + kt * 16 + (ln >> 5) * 8;
           float x[8];
 #pragma unroll
@@ -964,7 +972,7 @@ __device__ __forceinline__ void net313_body(const Net313Pair& pr) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int row = rb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-          if (row < a.M3) Y[(long)row * P + gcol] = cacc[jj][r];
+          if (row < a.M3 && gcol >= 0) Y[(long)row * P + gcol] = cacc[jj][r];
         }
       }
     } else {
@@ -985,8 +993,8 @@ __device__ __forceinline__ void net313_body(const Net313Pair& pr) {
         for (int ks = 0; ks < ksplit; ++ks) sum += part[((task * ksplit + ks) * 16 + r) * 64 + ln];
         const int rb = task / NB, b = task % NB;
         const int row = rb * 32 + (r & 3) + 8 * (r >> 2) + 4 * (ln >> 5);
-        const int n = b * 32 + (ln & 31), py = n / seg;
-        if (row < a.M3) Y[(long)row * P + (y0 + py) * a.W + x0 + (n - py * seg)] = sum;
+        const int gcol = gp_of(b * 32 + (ln & 31));
+        if (row < a.M3 && gcol >= 0) Y[(long)row * P + gcol] = sum;
       }
     }
     }   // rounds
@@ -1014,7 +1022,7 @@ enum { V64 = 0, VHALF = 1, VWIDE = 2 };
 
 static int tile_fits(int hid, int C, int H, int W, int bn, int ldsf) {
   if (!halo_tiles(H, W, bn)) return 0;
-  const long need = (long)hid * bn + halo_lds_floats(C, W, bn);
+  const long need = (long)hid * bn + halo_lds_floats(C, H, W, bn);
   return need <= ldsf - 32 - 8 * bn;       // last 16 floats: trace-partial slots; 16 + 8 x bn: H3 halo / column maxima
 }
 static int variant_fits(int hid, int C, int H, int W, int v) {
@@ -1026,6 +1034,21 @@ static int variant_fits(int hid, int C, int H, int W, int v) {
 int net313_supported(int hid, int C, int H, int W) {
   if (hid != 512 && hid != 256) return 0;
   return variant_fits(hid, C, H, W, V64) || variant_fits(hid, C, H, W, VHALF) || variant_fits(hid, C, H, W, VWIDE);
+}
+
+int net313_max_tiles(int hid, int C, int H, int W) {
+  int m = 0;
+  for (int v = V64; v <= VWIDE; ++v)
+    if (variant_fits(hid, C, H, W, v)) m = std::max(m, tile_count(H, W, v == V64 ? 64 : 32));
+  return m;
+}
+int net313_tile_pixels(int hid, int C, int H, int W) {
+  int m = 0;
+  for (int v = V64; v <= VWIDE; ++v) {
+    const int bn = v == V64 ? 64 : 32;
+    if (variant_fits(hid, C, H, W, v)) m = std::max(m, tile_count(H, W, bn) * bn);
+  }
+  return m;
 }
 
 // Launch one or two nets (same shape) as one grid.  The 64-pixel tile is used unless the grid would
@@ -1120,10 +1143,13 @@ int launch_net313_multi(const Net313Args* args, int nnets, int hid, int mode, hi
   // variant when neither fits
   const bool f64 = variant_fits(hid, a0.C, a0.H, a0.W, V64), fh = variant_fits(hid, a0.C, a0.H, a0.W, VHALF);
   int var = f64 ? V64 : (fh ? VHALF : VWIDE);
-  if (var == V64 && layout_nets * a0.B * (P / 64) < 256 && fh) var = VHALF;
+  // (grids counted in tiles: P / 64 and P / 32 on an exact shape, more on a ragged one.  A shape only the 64-pixel
+  // variant tiles, 32 < W < 64, keeps it however small the grid: fh is false there)
+  const int t64 = tile_count(a0.H, a0.W, 64), t32 = tile_count(a0.H, a0.W, 32);
+  if (var == V64 && layout_nets * a0.B * t64 < 256 && fh) var = VHALF;
   // at most one 32-pixel workgroup per CU anyway: the full-LDS variant (256 VGPRs, deeper operand
   // prefetch, paired phase-C jobs) beats the two-per-CU one (8x8 scale at B=64: 96 vs 102 us per term)
-  if (var == VHALF && layout_nets * a0.B * (P / 32) <= 256 && variant_fits(hid, a0.C, a0.H, a0.W, VWIDE)) var = VWIDE;
+  if (var == VHALF && layout_nets * a0.B * t32 <= 256 && variant_fits(hid, a0.C, a0.H, a0.W, VWIDE)) var = VWIDE;
   const int bn = var == V64 ? 64 : 32;
   Net313Pair pr;
   pr.a[0] = args[0];
@@ -1140,8 +1166,12 @@ int launch_net313_multi(const Net313Args* args, int nnets, int hid, int mode, hi
   const bool p64 = mode == MODE_VJP && k128_pol == 3 && h3_args && var == V64 &&
                    net313p_fits(hid, a0.C, a0.H, a0.W);
   const int tbn = p64 ? 64 : (k128 ? 128 : bn);
-  for (int i = 0; i < 2; ++i) pr.a[i].seg = a0.W < tbn ? a0.W : tbn;
-  pr.nb0 = a0.B * (P / tbn);
+  for (int i = 0; i < 2; ++i) {
+    pr.a[i].seg = tile_seg(a0.W, tbn);
+    pr.a[i].rows = tile_rows(a0.H, a0.W, tbn);
+    pr.a[i].tiles = tile_count(a0.H, a0.W, tbn);
+  }
+  pr.nb0 = a0.B * pr.a[0].tiles;
   pr.max_ksplit = 8;
   pr.dbg = (a0.exact_scale ? 16 : 0) | (a0.presplit ? 0 : 32);        // INF_OPT_K128_EXACT_SCALE: chunk 1's exact-scale path on every tile
   pr.reverse = a0.tile_order;

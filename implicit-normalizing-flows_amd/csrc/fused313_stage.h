@@ -12,14 +12,30 @@ namespace inf {
 // pixels of one image row that a bn-pixel tile covers: whole rows of a narrow image, a bn-wide segment of a wide one
 constexpr int tile_seg(int W, int bn) { return W < bn ? W : bn; }
 
-// host: an H x W image cuts into bn-pixel tiles of whole rows (W < bn) or of row segments (W >= bn)
-inline bool halo_tiles(int H, int W, int bn) {
+// host: an H x W image cuts into bn-pixel tiles of whole rows (W < bn) or of row segments (W >= bn) with no column of
+// a tile left over: the only geometry the 128-pixel and the two-per-CU kernels (fused313k.hip, fused313p.hip) take
+inline bool halo_tiles_exact(int H, int W, int bn) {
   const int seg = tile_seg(W, bn);
   return (H * W) % bn == 0 && bn % seg == 0 && !(W > bn && W % bn != 0);
 }
+// host: image rows of one tile.  Whole-row tiles (W <= bn) take as many rows as fit, floor(bn / W), and no more than the
+// image has; on an exact shape this is bn / seg
+inline int tile_rows(int H, int W, int bn) {
+  const int r = bn / tile_seg(W, bn);
+  return (W <= bn && H < r) ? H : r;
+}
+// host: fused313.hip's tiles.  Exact ones, or ragged whole-row tiles: rows * W <= bn live pixel columns and bn - rows * W
+// dead ones per tile, the last tile of an image possibly short of rows.  Segment tiles stay exact.
+inline bool halo_tiles(int H, int W, int bn) { return W <= bn || W % bn == 0; }
+// host: tiles per image (P / bn on an exact shape)
+inline int tile_count(int H, int W, int bn) {
+  if (W > bn) return H * (W / bn);
+  const int rows = tile_rows(H, W, bn);
+  return (H + rows - 1) / rows;
+}
 // host: LDS floats of the im2col offset table, the halo tile and its zero run (what HaloGeom::vhz() + K1pad come to)
-inline long halo_lds_floats(int C, int W, int bn) {
-  const int seg = tile_seg(W, bn), rows = bn / seg;
+inline long halo_lds_floats(int C, int H, int W, int bn) {
+  const int seg = tile_seg(W, bn), rows = tile_rows(H, W, bn);
   return (9L * C + 15) / 16 * 16 + (long)C * (rows + 2) * (seg + 2) + (long)rows * (seg + 2);
 }
 
@@ -35,6 +51,11 @@ struct HaloGeom {
   // phase A reads vh[koff + pix], so the zero run must cover every pixel offset of the tile: rows * CW floats (a
   // single zero slot there once let padded rows read LDS the kernel never wrote)
   __device__ __forceinline__ int vhz() const { return vhn() + rows * CW(); }
+  // Ragged whole-row tiles: the rows of this tile that lie in the image (the last tile of an image may be short), and
+  // its live pixel columns n < live_cols() (n = row * seg + x); the other columns of the bn are dead.  On an exact
+  // shape every column is live.
+  __device__ __forceinline__ int live_rows() const { return min(rows, H - y0); }
+  __device__ __forceinline__ int live_cols() const { return live_rows() * seg; }
 };
 
 // Stages the halo tile into vh[0, vhz) with NT threads; hmx / dacc receive this thread's max |value| and its part of
@@ -96,6 +117,8 @@ __device__ __forceinline__ void stage_halo(const Net313Args& a, const HaloGeom& 
         const int hy = rr / CW, hx = rr - hy * CW;
         const int yy = y0 + hy - 1, xx = x0 + hx - 1;
         const bool in_img = i < vhn && yy >= 0 && yy < H && xx >= 0 && xx < W;
+        // ok == 2: the tile's own pixels.  A short last tile needs no live_rows() here: its missing rows lie below the
+        // image, so in_img already excludes them
         const int ok = in_img ? ((hy >= 1 && hy <= rows && hx >= 1 && hx <= seg) ? 2 : 1) : 0;
         float v = 0.f;
 #pragma unroll

@@ -53,9 +53,11 @@ constexpr int KB_TSLOTS = 32;
 // 128-pixel tiles fit: whole image rows (or a 128-wide row segment), halo + im2col table + chunk buffer
 int net313k_fits(int hid, int C, int H, int W) {
   if (hid != KB_HID) return 0;
-  if (!halo_tiles(H, W, KB_BN)) return 0;
+  // exact tiles only, which also makes the 64-pixel tiles whose d1 / d2 layout this kernel shares exact (ragged shapes
+  // stay on fused313.hip's 64-pixel kernel)
+  if (!halo_tiles_exact(H, W, KB_BN)) return 0;
   if (9 * C > 256) return 0;                      // phase A: at most 16 K tiles
-  const long need = KB_CHUNK + KB_NW * KB_BN + 8 + 2 * KB_NW + 4 + halo_lds_floats(C, W, KB_BN);
+  const long need = KB_CHUNK + KB_NW * KB_BN + 8 + 2 * KB_NW + 4 + halo_lds_floats(C, H, W, KB_BN);
   return need <= KB_LDS;
 }
 

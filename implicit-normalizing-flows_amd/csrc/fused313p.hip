@@ -34,9 +34,10 @@ constexpr int PB_LDS = 19968;       // floats (78 KiB): two workgroups per CU
 
 int net313p_fits(int hid, int C, int H, int W) {
   if (hid != PB_HID) return 0;
-  if (!halo_tiles(H, W, PB_BN) || tile_seg(W, PB_BN) % 4 != 0) return 0;
+  // exact tiles only (ragged shapes stay on fused313.hip's 64-pixel kernel)
+  if (!halo_tiles_exact(H, W, PB_BN) || tile_seg(W, PB_BN) % 4 != 0) return 0;
   if (9 * C > 256) return 0;                      // phase A: at most 16 K tiles
-  const long need = PB_CHUNK + PB_NW * PB_BN + 8 + 2 * PB_NW + 4 + halo_lds_floats(C, W, PB_BN);
+  const long need = PB_CHUNK + PB_NW * PB_BN + 8 + 2 * PB_NW + 4 + halo_lds_floats(C, H, W, PB_BN);
   return need <= PB_LDS;
 }
 

@@ -203,10 +203,12 @@ struct Net313Args {
   const float* beta1;
   const float* b2;
   const float* beta2;
-  float* d1;              // swish'(a1), B*HID*H*W floats in MFMA-fragment order (fused313.hip dfrag)
+  float* d1;              // swish'(a1), B*HID*tiles*(tile width) floats (= B*HID*H*W on an exact shape) in MFMA-fragment
+                          // order per tile (fused313.hip dfrag)
   float* d2;              // swish'(a2), same layout
   float* Y;               // (B, M3, H, W) packed taps
   int B, C, H, W, seg;
+  int rows, tiles;        // the launch's tile geometry (set by launch_net313_multi): image rows per tile, tiles per image
   // VJP series chaining (conv_out folded into the next term's halo staging):
   const float* in_taps;   // non-null: the input v is the previous term's packed taps (B, M3, H, W),
                           // v = sum of the 9 shifted taps (zero padded), replaces `in`
@@ -242,6 +244,10 @@ __device__ __forceinline__ int pair_tile(const Net313Pair& pr, int bx, int& sel)
   return bx - (sel ? pr.nb0 : 0);
 }
 int net313_supported(int hid, int C, int H, int W);
+// Over the variants that fit the shape: the most tiles per image, and the most pixel columns per image (tiles x tile
+// width) of the tile-indexed d1 / d2 layout.  H * W / 32 at most and H * W on an exact shape; more on a ragged one.
+int net313_max_tiles(int hid, int C, int H, int W);
+int net313_tile_pixels(int hid, int C, int H, int W);
 // 128-pixel K-chunked variant (fused313k.hip, INF_MFMA_F16X3 only): MODE_VJP and MODE_EVAL
 int net313k_fits(int hid, int C, int H, int W);
 int launch_net313k(const Net313Pair& pr, int mode, unsigned nb, hipStream_t s);

@@ -4,6 +4,7 @@
 * ``CIFAR10Binary``                -- the CIFAR-10 binary distribution (``cifar-10-batches-bin``),
   giving what ``torchvision.datasets.CIFAR10`` + ``ToTensor`` give train_img.py:231-252 (torchvision
   is not installed here; the binary files need no unpickling)
+* ``read_mnist_idx``               -- the MNIST distribution's idx3 / idx1 ubyte files (train_img.py:256-270)
 * ``power_splits`` / ``load_power`` -- the POWER preprocessing of lib/tabular.py:137-163
 
 All of this is host-side plumbing; the tensors it produces feed the engine unchanged.
@@ -13,7 +14,7 @@ import os
 import numpy as np
 import torch
 
-__all__ = ['add_noise', 'reduce_bits', 'CIFAR10Binary', 'power_splits', 'load_power', 'normalize_raw_data',
+__all__ = ['add_noise', 'reduce_bits', 'CIFAR10Binary', 'read_mnist_idx', 'power_splits', 'load_power', 'normalize_raw_data',
            'make_tabular_train_valid_split', 'make_tabular_train_valid_test_split']
 
 
@@ -68,6 +69,36 @@ class CIFAR10Binary(torch.utils.data.Dataset):
         if self.transform is not None:
             x = self.transform(x)
         return x, int(self.labels[i])
+
+
+def _idx_array(path, magic, ndim):
+    """One idx ubyte file: a big-endian header of the magic number (two zero bytes, the type code 0x08 for unsigned
+    bytes, the number of dimensions) and one 32-bit size per dimension, then the bytes in C order."""
+    buf = np.fromfile(path, dtype=np.uint8)
+    head = 4 * (1 + ndim)
+    if buf.size < head:
+        raise ValueError('%s: %d bytes is shorter than an idx%d header' % (path, buf.size, ndim))
+    words = buf[:head].view('>u4')
+    if int(words[0]) != magic:
+        raise ValueError('%s: magic number %d, expected %d' % (path, int(words[0]), magic))
+    dims = tuple(int(w) for w in words[1:])
+    n = int(np.prod(dims, dtype=np.int64))
+    if buf.size - head != n:
+        raise ValueError('%s: header says %s = %d bytes, the file holds %d' % (path, dims, n, buf.size - head))
+    return buf[head:].reshape(dims)
+
+
+def read_mnist_idx(images_path, labels_path=None):
+    """MNIST's ``*-images-idx3-ubyte`` (magic 2051) and, if given, ``*-labels-idx1-ubyte`` (magic 2049), uncompressed.
+    Returns the images as a uint8 (N, 1, H, W) tensor (28 x 28 for MNIST itself), or (images, int64 labels (N,)).
+    A wrong magic number, a truncated file or a label count other than N raises ValueError."""
+    images = torch.from_numpy(_idx_array(images_path, 2051, 3).copy()).unsqueeze(1)
+    if labels_path is None:
+        return images
+    labels = _idx_array(labels_path, 2049, 1)
+    if labels.shape[0] != images.shape[0]:
+        raise ValueError('%s: %d labels for %d images' % (labels_path, labels.shape[0], images.shape[0]))
+    return images, torch.from_numpy(labels.astype(np.int64))
 
 
 # ---- POWER (lib/tabular.py:43-60,137-163) --------------------------------------------------------

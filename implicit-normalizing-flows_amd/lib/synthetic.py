@@ -41,6 +41,12 @@ CIFAR10_SMALL = dict(CIFAR10, idim=64)
 # CelebA-HQ 256, 5 bits: C3 architecture with 4 scales.
 CELEBAHQ256 = dict(CIFAR10, input_size=(3, 256, 256), n_blocks=[2, 2, 2, 2], nvals=32)
 
+# --data mnist at --imagesize 28 (train_img.py:256-258: one channel, LogitTransform(1e-6)): scales of 28x28, 14x14 and
+# 7x7, none of which cuts into whole 32- or 64-pixel tiles (the fused kernels' ragged tiles).
+MNIST = dict(CIFAR10, input_size=(1, 28, 28), init_alpha=1e-6)
+# One block per scale at idim 256: the fixture of tests/golden/make_golden_ragged.py.
+MNIST_SMALL = dict(MNIST, n_blocks=[1, 1, 1], idim=256)
+
 # run_tabular.sh:1-2 (POWER): 20 blocks, 6-128x4-6, sin, coeff .99, epsf 1e-5, geometric.
 POWER = dict(
     kind='fc', d=6, dims=[128, 128, 128, 128], n_blocks=20, act='sin', coeff=0.99,
@@ -59,7 +65,7 @@ TOY = dict(
 POWER_EXACT = dict(POWER, exact_trace=True)
 
 CONFIGS = {'cifar10': CIFAR10, 'cifar10_small': CIFAR10_SMALL, 'celebahq256': CELEBAHQ256,
-           'power': POWER, 'toy': TOY, 'power_exact': POWER_EXACT}
+           'power': POWER, 'toy': TOY, 'power_exact': POWER_EXACT, 'mnist': MNIST, 'mnist_small': MNIST_SMALL}
 
 # The activation table's other entries (implicit_flow.py ACT_FNS) on the architectures above: the fixtures of
 # tests/golden/make_golden_acts.py.  Only Swish has a parameter, so these state dicts hold no '.beta' keys.
