@@ -229,7 +229,8 @@ size_t carve(const InfNet* n, int B, int T, void* ws, size_t cap, Bufs& b) {
   const size_t E = (size_t)B * n->d;
   const size_t Hs = (size_t)B * per_sample_hidden(n);
   const size_t Ys = (size_t)B * n->rows_max * (n->fc ? 1 : n->P);
-  const int nchunk = n->fc ? 1 : out_nchunk(n->d);
+  // (narrow fc nets: one partial per sample; wide fc nets and conv nets: one per OUT_CH-element chunk)
+  const int nchunk = n->fc ? fc_nchunk(n->d) : out_nchunk(n->d);
   b.nchunk = nchunk;
   b.snchunk = n->fused ? std::max(nchunk, std::max(n->P / 32, n->ftiles)) : nchunk;
   b.h0 = w.take<float>(Hs);
@@ -244,7 +245,7 @@ size_t carve(const InfNet* n, int B, int T, void* ws, size_t cap, Bufs& b) {
   for (float** v : vecs) *v = w.take<float>(E);
   b.U = w.take<float>((size_t)T * E);
   b.VT = w.take<float>((size_t)T * E);
-  if (n->fc) {
+  if (n->fc && n->d <= 16) {   // forward-mode tangents (fc_jacobian): every user declines d > 16
     const size_t ext = (size_t)(n->d + 1) * B * std::max(n->hidden_max, n->d);
     b.ext0 = w.take<float>(ext);
     b.ext1 = w.take<float>(ext);
@@ -496,7 +497,7 @@ int run_vjp(InfNet* n, const float* v, float* vout, const float* xin, const floa
   a.pre_beta = n->pre_beta;
   a.pre_act = n->pre_act;
   a.partial = partial;
-  a.nchunk = n->fc ? 1 : out_nchunk(n->d);
+  a.nchunk = n->fc ? fc_nchunk(n->d) : out_nchunk(n->d);
   return n->fc ? launch_fc_out(a, B, s) : launch_conv_out(a, B, s);
 }
 
@@ -538,10 +539,11 @@ struct PsStep {
   long sb = 0, si = 0;
 };
 int enqueue_sumsq(InfNet* f, int B, Bufs& bf, SumsSlot* sl, hipStream_t s, const PsStep* ps = nullptr) {
-  // fc nets write one partial per sample: with the global rule those are the sums already (0 + x == x for the
-  // non-negative or NaN sums), so the readback takes them directly and the reduction launch is skipped
+  // narrow fc nets write one partial per sample: with the global rule those are the sums already (0 + x == x for the
+  // non-negative or NaN sums), so the readback takes them directly and the reduction launch is skipped (wide fc nets
+  // write chunk partials, as conv nets)
   const bool ps_on = ps && ps->on;
-  const bool direct = (f->fc || bf.sample_sums) && !ps_on;
+  const bool direct = ((f->fc && bf.nchunk == 1) || bf.sample_sums) && !ps_on;
   if (direct && bf.part == sl->host) {               // the residual launch wrote the sums into the slot itself
     const bool bound = bf.stop_bound && bf.stop_ev == sl->ev;
     bf.stop_bound = false;
@@ -552,11 +554,11 @@ int enqueue_sumsq(InfNet* f, int B, Bufs& bf, SumsSlot* sl, hipStream_t s, const
   }
   if (!direct && !ps_on) {                            // global rule: the reduction writes the sums into the slot
     bool bound = false;                              // (and completes the slot's event itself: no marker packet)
-    INF_TRY(launch_reduce_partials(bf.part, B, f->fc ? 1 : bf.nchunk, sl->host, s, sl->ev, &bound));
+    INF_TRY(launch_reduce_partials(bf.part, B, bf.nchunk, sl->host, s, sl->ev, &bound));
     if (!bound) INF_HIP(hipEventRecord(sl->ev, s));
     return INF_OK;
   }
-  if (!direct) INF_TRY(launch_reduce_partials(bf.part, B, f->fc ? 1 : bf.nchunk, bf.sumsq, s));
+  if (!direct) INF_TRY(launch_reduce_partials(bf.part, B, bf.nchunk, bf.sumsq, s));
   int n = B;
   if (ps_on) {
     INF_TRY(launch_ps_decide(bf.sumsq, bf.ps_state, bf.ps_active, bf.ps_improved, B, ps->k, ps->T, ps->eps, s));
@@ -638,7 +640,7 @@ int eval_resid(InfNet* f, const float* z, const float* zsub, const float* xemb, 
 int vjp_resid_part(InfNet* f, const float* y, const float* zi, const float* gradi, float* gout, float* dg,
                    const float* gprev, int B, Bufs& bf, hipStream_t s) {
   INF_TRY(run_vjp(f, y, bf.tmp, zi, nullptr, nullptr, B, bf, s));
-  return launch_vjp_resid(bf.tmp, y, gradi, gprev, gout, dg, bf.part, B, f->d, f->fc ? 1 : bf.nchunk, f->fc, s);
+  return launch_vjp_resid(bf.tmp, y, gradi, gprev, gout, dg, bf.part, B, f->d, bf.nchunk, f->fc, s);
 }
 
 double total(const std::vector<double>& v) {
@@ -788,7 +790,7 @@ int broyden_core(InfNet* f, const ResidFn& resid, int B, int T, double eps_in, I
   // eval_resid_part / resid_bcast, d <= 4 residual chunks per sample): the residual launch itself sums each sample
   // over its chunks (one block per sample, conv_out_resid_sample_kernel) into the slot, so no reduction launch sits
   // between it and the readback either.  (The implicit backward's residual writes chunk partials: not here.)
-  const bool zc = (f->fc || (resid_sample_sums && out_nchunk(f->d) <= 4)) && !per_sample;
+  const bool zc = ((f->fc && bf.nchunk == 1) || (!f->fc && resid_sample_sums && out_nchunk(f->d) <= 4)) && !per_sample;
   struct PartRestore {
     Bufs& b;
     double* p;
@@ -1339,7 +1341,8 @@ int broyden_solve(InfNet* f, const float* y, int B, int T, double eps_in, InfBro
     INF_TRY(broyden_core_ls(f, resid, B, T, eps_in, stats, lowest_ss, bf, s, /*keep_f=*/true));
   } else {
     INF_TRY(broyden_core(f, resid, B, T, eps_in, stats, lowest_ss, bf, s, /*keep_f=*/true, f->fcfused ? &step : nullptr,
-                         (f->fc || conv_start) ? &start : nullptr, tail, /*resid_sample_sums=*/true));
+                         ((f->fc && f->d <= FC_NARROW_MAX) || conv_start) ? &start : nullptr, tail,
+                         /*resid_sample_sums=*/true));
   }
   if (diff_detail) {
     std::vector<float> dd(B);
@@ -1812,7 +1815,6 @@ int inf_net_create(const InfNetDesc* desc, InfNet** out) {
     ch = w.cout;
   }
   if (ch != n->C) { delete n; return INF_ERR_UNSUPPORTED; }
-  if (n->fc && n->C > 32) { delete n; return INF_ERR_UNSUPPORTED; }
   // plans
   size_t floats = 0;
   for (int l = 0; l < L; ++l) {

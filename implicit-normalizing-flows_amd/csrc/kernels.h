@@ -70,7 +70,12 @@ struct OutArgs {
 int out_nchunk(int per_sample);
 int launch_conv_out(const OutArgs& a, int batch, hipStream_t s);
 
-// fc nets: feature-major (d, B) tensors, one thread per sample for the per-sample reductions.
+// fc nets: feature-major (d, B) tensors.  Up to FC_NARROW_MAX features: one thread per sample for the per-sample
+// reductions, one partial per sample (nchunk = 1).  Wider nets: a grid over (feature chunk, sample block) with
+// out_nchunk(d) partials per sample, as conv_out (pointwise.hip fc_out_wide_kernel); so do launch_resid_bcast_fc and
+// launch_vjp_resid.
+constexpr int FC_NARROW_MAX = 32;
+inline int fc_nchunk(int d) { return d > FC_NARROW_MAX ? out_nchunk(d) : 1; }
 int launch_fc_out(const OutArgs& a, int batch, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------

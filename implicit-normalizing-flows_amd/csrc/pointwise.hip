@@ -4,6 +4,7 @@
 // reduce per sample with wave shuffles + one LDS stage; cross-block sums go through fixed-order
 // fp64 partial slabs (deterministic, no float atomics).
 #include <algorithm>
+#include <cstring>
 
 #include "kernels.h"
 
@@ -18,6 +19,9 @@ struct CoeffTable {
 };
 
 int out_nchunk(int per_sample) { return (per_sample + OUT_CH - 1) / OUT_CH; }
+// the wide fc output stage (below); mode: an OutMode or OM_WIDE_VJPRES
+constexpr int OM_WIDE_VJPRES = 5;
+static int launch_fc_out_wide(const OutArgs& a, int batch, int mode, int bcast, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------
 // conv net output stage.  Y holds packed taps Y[b][c*9+t][p] (KS = 3) or rows Y[b][c][p] (KS = 1).
@@ -380,6 +384,19 @@ int launch_broyden_start_fc(const float* f0, const float* xemb, float* x0, float
 }
 int launch_resid_bcast_fc(const float* f0, const float* xemb, const float* z, float* g, float* fcur, double* partial,
                           int batch, int d, hipStream_t s) {
+  if (d > FC_NARROW_MAX) {                     // wide nets: fc_out_wide's OM_RESID with Y = f0 broadcast, chunk partials
+    OutArgs a;
+    memset(&a, 0, sizeof(a));
+    a.Y = f0;
+    a.C = d;
+    a.in0 = xemb;
+    a.in1 = z;
+    a.out0 = g;
+    a.out2 = fcur;
+    a.partial = partial;
+    a.nchunk = out_nchunk(d);
+    return launch_fc_out_wide(a, batch, OM_RESID, 1, s);
+  }
   INF_PROF_LAUNCH(s, 701, 16.0 * batch * d + 8.0 * batch, resid_bcast_fc_kernel, dim3((batch + 255) / 256),
                   dim3(256), 0, s, f0, xemb, z, g, fcur, partial, batch, d);
   return INF_OK;
@@ -423,6 +440,20 @@ __global__ void vjp_resid_fc_kernel(const float* v, const float* y, const float*
 }
 int launch_vjp_resid(const float* v, const float* y, const float* grad, const float* gprev, float* g, float* dg,
                      double* partial, int batch, int d, int nchunk, int fc, hipStream_t s) {
+  if (fc && d > FC_NARROW_MAX) {               // wide fc nets: partial[b * nchunk + chunk]
+    OutArgs a;
+    memset(&a, 0, sizeof(a));
+    a.Y = v;
+    a.C = d;
+    a.in0 = y;
+    a.in1 = grad;
+    a.in2 = gprev;
+    a.out0 = g;
+    a.out1 = dg;
+    a.partial = partial;
+    a.nchunk = nchunk;
+    return launch_fc_out_wide(a, batch, OM_WIDE_VJPRES, 0, s);
+  }
   if (fc) {
     hipLaunchKernelGGL(vjp_resid_fc_kernel, dim3((batch + 255) / 256), dim3(256), 0, s, v, y, grad, gprev, g, dg,
                        partial, d, batch);
@@ -473,7 +504,91 @@ __global__ __launch_bounds__(256) void fc_out_kernel(OutArgs a, int batch) {
   if (a.partial) a.partial[b] = acc;
 }
 
+// Wide fc nets (d > FC_NARROW_MAX): the same epilogues on a grid of (feature chunk of OUT_CH rows, sample block of
+// 2^lsb columns).  A thread owns one sample column of its block and every (OUT_CH >> lsb)-th feature row of the chunk,
+// so a wave's loads run along the contiguous batch index of the (d, B) layout (and over consecutive rows when the
+// block is narrower than a wave).  The per-sample fp64 partial of a chunk: each thread's rows in row order, then a
+// fixed LDS tree over the threads of the column; partial[b * nchunk + chunk], summed in chunk order by
+// reduce_partials_kernel / series_combine_kernel -- nothing depends on scheduling.
+//   bcast: Y holds d values (the cached f(0), bias included) broadcast over the batch (resid_bcast_fc's residual)
+//   OM_WIDE_VJPRES (internal): the implicit backward's residual, g = (in0 + Y) - in1 with Y = y^T J, in0 = y, in1 = grad
+template <int MODE>
+__global__ __launch_bounds__(OUT_CH) void fc_out_wide_kernel(OutArgs a, int batch, int lsb, int bcast) {
+  __shared__ double red[OUT_CH];
+  const int sbw = 1 << lsb;
+  const int chunk = blockIdx.x, tid = threadIdx.x;
+  const int b = blockIdx.y * sbw + (tid & (sbw - 1));
+  const int lo = chunk * OUT_CH, hi = min(a.C, lo + OUT_CH), rstep = OUT_CH >> lsb;
+  const float sp = (MODE == OM_VJP && a.pre_beta) ? softplus_f(ldc(a.pre_beta)) : 0.f;
+  double acc = 0.0;
+  if (b < batch) {
+#pragma unroll 4
+    for (int c = lo + (tid >> lsb); c < hi; c += rstep) {
+      const long ei = (long)c * batch + b;
+      const float s = bcast ? a.Y[c] : a.Y[ei];
+      if constexpr (MODE == OM_PLAIN) {
+        a.out0[ei] = s + a.bias[c];
+      } else if constexpr (MODE == OM_EMBED) {
+        const float v = s + a.bias[c];
+        a.out0[ei] = v;
+        a.out1[ei] = v + a.in0[ei];
+      } else if constexpr (MODE == OM_RESID) {
+        const float v = a.bias ? s + a.bias[c] : s;
+        const float gx = (a.in0[ei] - v) - a.in1[ei];
+        a.out0[ei] = gx;
+        if (a.in2) a.out1[ei] = gx - a.in2[ei];
+        if (a.out2) a.out2[ei] = v;
+        acc += (double)gx * (double)gx;
+      } else if constexpr (MODE == OM_RECOMP) {
+        a.out0[ei] = (a.in0[ei] - (s + a.bias[c])) + a.in1[ei];
+      } else if constexpr (MODE == OM_VJP) {
+        float v = s;
+        if (a.pre_beta) v = v * swish_d(a.in1[ei], sp);
+        else if (a.pre_act != ACT_NONE) v = v * act_any_d(a.pre_act, a.in1[ei]);
+        a.out0[ei] = v;
+        if (a.partial) acc += (double)v * (double)a.in0[ei];
+      } else {
+        const float gv = (a.in0[ei] + s) - a.in1[ei];
+        a.out0[ei] = gv;
+        if (a.in2) a.out1[ei] = gv - a.in2[ei];
+        acc += (double)gv * (double)gv;
+      }
+    }
+  }
+  if constexpr (MODE == OM_RESID || MODE == OM_VJP || MODE == OM_WIDE_VJPRES) {
+    if (!a.partial) return;                      // (uniform over the block)
+    red[tid] = acc;
+    __syncthreads();
+    for (int st = OUT_CH / 2; st >= sbw; st >>= 1) {
+      if (tid < st) red[tid] += red[tid + st];
+      __syncthreads();
+    }
+    if (tid < sbw && b < batch) a.partial[(long)b * a.nchunk + chunk] = red[tid];
+  }
+}
+
+static int launch_fc_out_wide(const OutArgs& a, int batch, int mode, int bcast, hipStream_t s) {
+  const int nch = out_nchunk(a.C);
+  if (a.partial && a.nchunk != nch) return INF_ERR_INVALID;
+  if ((mode == OM_RESID || mode == OM_WIDE_VJPRES) && !a.partial) return INF_ERR_INVALID;
+  int lsb = 0;
+  while (lsb < 6 && (1 << lsb) < batch) ++lsb;   // sample block: the batch rounded up to a power of two, a wave at most
+  const dim3 grid(nch, (batch + (1 << lsb) - 1) >> lsb);
+  // bytes: Y and ~3 per-element vectors in / out
+  const double by = 16.0 * (double)batch * a.C;
+#define FCW_K(M_)                                                                                                  \
+  case M_:                                                                                                         \
+    INF_PROF_LAUNCH(s, 950 + M_, by, fc_out_wide_kernel<M_>, grid, dim3(OUT_CH), 0, s, a, batch, lsb, bcast);       \
+    return INF_OK;
+  switch (mode) {
+    FCW_K(OM_PLAIN) FCW_K(OM_EMBED) FCW_K(OM_RESID) FCW_K(OM_RECOMP) FCW_K(OM_VJP) FCW_K(OM_WIDE_VJPRES)
+  }
+#undef FCW_K
+  return INF_ERR_INVALID;
+}
+
 int launch_fc_out(const OutArgs& a, int batch, hipStream_t s) {
+  if (a.C > FC_NARROW_MAX) return launch_fc_out_wide(a, batch, a.mode, 0, s);
   hipLaunchKernelGGL(fc_out_kernel, dim3((batch + 255) / 256), dim3(256), 0, s, a, batch);
   INF_CHECK_LAUNCH();
   return INF_OK;

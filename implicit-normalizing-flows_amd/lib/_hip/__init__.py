@@ -523,6 +523,8 @@ def tag_name(tag):
         return 'fcseries_kernel'
     if tag in WGRAD_TAGS:
         return WGRAD_TAGS[tag]
+    if 950 <= tag <= 955:    # output stage of fc nets wider than 32 features (pointwise.hip), 95<mode>
+        return 'fc_out_wide_kernel<%s>' % ['PLAIN', 'EMBED', 'RESID', 'RECOMP', 'VJP', 'VJPRES'][tag - 950]
     if 800 <= tag < 900:     # tiled weight-gradient kernel (grad.hip), 8<TMW><TNW>
         return 'wgrad_tiled_kernel<%d,%d>' % ((tag - 800) // 10, tag % 10)
     if tag < 1000:

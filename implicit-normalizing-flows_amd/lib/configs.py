@@ -13,10 +13,11 @@ def build_flow(arch, batch=64):
         c, h, w = arch['input_size']
         return ImplicitFlow(
             (batch, c, h, w), n_blocks=arch['n_blocks'], intermediate_dim=arch['idim'], factor_out=False,
-            init_layer=layers.LogitTransform(arch['init_alpha']), actnorm=arch['actnorm'], fc=False,
+            init_layer=layers.LogitTransform(arch['init_alpha']), actnorm=arch['actnorm'], fc=arch.get('fc', False),
             coeff=arch['coeff'], vnorms=arch.get('vnorms', '2222'), sn_atol=1e-3, sn_rtol=1e-3, n_power_series=None,
-            n_dist=arch['n_dist'], n_samples=1, kernels=arch['kernels'], activation_fn=arch['act'], fc_end=False,
-            n_exact_terms=arch['n_exact_terms'], preact=arch['preact'], neumann_grad=True, grad_in_forward=True)
+            n_dist=arch['n_dist'], n_samples=1, kernels=arch['kernels'], activation_fn=arch['act'],
+            fc_end=arch.get('fc_end', False), fc_idim=arch.get('fc_idim', 128), n_exact_terms=arch['n_exact_terms'],
+            preact=arch['preact'], neumann_grad=True, grad_in_forward=True)
     d = arch['d']
     dims = [d] + list(arch['dims']) + [d]
 

@@ -7,7 +7,8 @@ forward threads (x, logpx) through the MI355X-backed layers of ``lib.layers``.
 Supported: conv or fc residual nets with InducedNorm layers (with or without bias; any vnorms whose norm pairs the
 reference's factories give to InducedNorm layers, e.g. '2222', '2332', '13f1': DESIGN.md §15), every
 activation of ACT_FNS (Swish, ELU, Softplus and ReLU on the fused 3-1-3 conv kernels, the others on the per-layer
-path), preact, ActNorm (2d and fc), LogitTransform init layer, squeeze, factor_out, fc_end.
+path), preact, ActNorm (2d and fc), LogitTransform init layer, squeeze, factor_out, fc_end and fc (fully connected
+blocks over the flattened sample, any width: DESIGN.md §17).
 Not provided (outside the density-evaluation hot path): quadratic / InvertibleConv,
 MovingBatchNorm, dropout, learn_p (a learnable norm order), the closed-form LopConv2d / LopLinear layers that the
 reference's factories pick for the norm pairs 1 -> {1, 2, inf} and {2, inf} -> inf (its class default vnorms='122f'

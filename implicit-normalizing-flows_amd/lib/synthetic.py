@@ -87,6 +87,16 @@ CONFIGS['cifar10_small_13f1'] = dict(CIFAR10_SMALL, vnorms='13f1')
 CONFIGS['cifar10_13f1'] = dict(CIFAR10, vnorms='13f1')
 CONFIGS['fc_2332'] = dict(POWER, dims=[32, 32], n_blocks=4, vnorms='2332')
 
+# Fully connected blocks over more than 32 features (the fixtures of tests/golden/make_golden_widefc.py).
+# Image flows on 3 x 8 x 8 (two scales, d = 192 flattened at both): ImplicitFlow(fc_end=True) -- its class default -- ends
+# the last scale in two imBlock(FCNet, FCNet) of width fc_idim, each followed by an ActNorm1d; ImplicitFlow(fc=True)
+# makes every block and every ActNorm fully connected.  Tabular flows at the widths of MINIBOONE (43) and BSDS300 (63).
+FCEND_SMALL = dict(CIFAR10_SMALL, input_size=(3, 8, 8), n_blocks=[1, 1], fc_end=True, fc_idim=128)
+FC_IMG_SMALL = dict(CIFAR10_SMALL, input_size=(3, 8, 8), n_blocks=[1, 1], fc=True)
+TAB_D43 = dict(POWER, d=43, n_blocks=4)
+TAB_D63 = dict(POWER, d=63, n_blocks=4)
+CONFIGS.update(fcend_small=FCEND_SMALL, fc_img_small=FC_IMG_SMALL, tab_d43=TAB_D43, tab_d63=TAB_D63)
+
 
 # Layers of the mixed-norm power-iteration fixtures (make_golden_vnorms.py): the smallest shapes that reach every
 # normalisation path of csrc/power.hip.  (name, kind, cin, cout, k, hw, [(domain, codomain), ...]); the first pair
@@ -147,24 +157,48 @@ def n_scales(input_size, n_blocks):
 
 
 def conv_flow_layout(arch):
-    """Chain layout of ImplicitFlow(factor_out=False, fc_end=False) (implicit_flow.py:101-139,411-434).
+    """Chain layout of ImplicitFlow(factor_out=False) (implicit_flow.py:101-139,411-434) with fc = arch.get('fc', False)
+    and fc_end = arch.get('fc_end', False).
 
     Returns a list of scales; each scale is a list of (kind, info) in chain order with kind in
-    {'logit', 'actnorm', 'imblock', 'squeeze'}.  imblock info holds the (C,H,W) it acts on and
-    its net layer list [(act,), ('conv', cin, cout, k), ...] with act = arch['act'].
+    {'logit', 'actnorm', 'imblock', 'squeeze', 'fc_actnorm', 'fc_imblock'}.  imblock info holds the (C,H,W) it acts on
+    and its net layer list [(act,), ('conv', cin, cout, k), ...] with act = arch['act'].  The fc kinds (fc / fc_end
+    flows only): 'fc_imblock' is an imBlock of two FCNet over the flattened (C,H,W) (net: [(act,), ('linear', a, b),
+    ...] under the key '<net>.nnet', a leading activation whenever preact), 'fc_actnorm' an FCWrapper(ActNorm1d(n))
+    (keys under '.fc_module').
     """
     c, h, w = arch['input_size']
     ks = list(map(int, arch['kernels'].split('-')))
+    fc, fc_end = arch.get('fc', False), arch.get('fc_end', False)
     scales = []
     ns = n_scales(arch['input_size'], arch['n_blocks'])
+
+    def fc_block(width):                      # FCNet (implicit_flow.py:437-474): len(ks) - 1 hidden layers
+        d = c * h * w
+        net = [(arch['act'],)] if arch['preact'] else []
+        last = d
+        for _ in range(len(ks) - 1):
+            net += [('linear', last, width), (arch['act'],)]
+            last = width
+        net.append(('linear', last, d))
+        return ('fc_imblock', dict(shape=(c, h, w), net=net))
+
+    def actnorm():
+        return ('fc_actnorm', dict(n=c * h * w)) if fc else ('actnorm', dict(c=c))
+
     for i in range(ns):
         chain = []
         first = (i == 0)
         if first:
             chain.append(('logit', dict(alpha=arch['init_alpha'])))
             if arch['actnorm']:
-                chain.append(('actnorm', dict(c=c)))
+                chain.append(actnorm())
         for b in range(arch['n_blocks'][i]):
+            if fc:
+                chain.append(fc_block(arch['idim']))
+                if arch['actnorm']:
+                    chain.append(actnorm())
+                continue
             first_block = first and b == 0
             net = []
             if not first_block and arch['preact']:
@@ -181,6 +215,11 @@ def conv_flow_layout(arch):
         if i < ns - 1:
             chain.append(('squeeze', dict(factor=2)))
             c, h, w = c * 4, h // 2, w // 2
+        elif fc_end:                          # two fc blocks at the end of the last scale (implicit_flow.py:429-433)
+            for _ in range(2):
+                chain.append(fc_block(arch.get('fc_idim', 128)))
+                if arch['actnorm']:
+                    chain.append(('fc_actnorm', dict(n=c * h * w)))
         scales.append(chain)
     return scales
 
@@ -299,14 +338,15 @@ def _net_entries(sd, prefix, net, hw, seed, power_iters, norms=None):
             sd[key + '.beta'] = _t([_rng(seed, key).uniform(0.3, 0.8)])
 
 
-def _imblock_entries(sd, prefix, info, arch, seed, power_iters):
-    hw = info['shape'][1:] if len(info['shape']) == 3 else None
+def _imblock_entries(sd, prefix, info, arch, seed, power_iters, sub=''):
+    """sub: '.nnet' for the FCNet branches of an fc block inside an image flow (their layers sit one level down)."""
+    hw = info['shape'][1:] if len(info['shape']) == 3 and not sub else None
     sd[prefix + '.lamb'] = torch.tensor(float(arch['lamb']))
     sd[prefix + '.last_n_samples'] = torch.zeros(1)
     sd[prefix + '.last_firmom'] = torch.zeros(1)
     sd[prefix + '.last_secmom'] = torch.zeros(1)
     for net in ('nnet_x', 'nnet_z'):
-        _net_entries(sd, prefix + '.' + net, info['net'], hw, seed, power_iters, layer_norms(arch))
+        _net_entries(sd, prefix + '.' + net + sub, info['net'], hw, seed, power_iters, layer_norms(arch))
     # frozen copies (implicit_block.py:136-141), refreshed from the nets every forward (:228-229)
     for net in ('nnet_x', 'nnet_z'):
         for k in list(sd.keys()):
@@ -329,6 +369,13 @@ def make_state_dict(arch, seed=0, power_iters=30):
                     sd[prefix + '.initialized'] = torch.tensor(1)
                 elif kind == 'imblock':
                     _imblock_entries(sd, prefix, info, arch, seed, power_iters)
+                elif kind == 'fc_actnorm':
+                    rng = _rng(seed, prefix)
+                    sd[prefix + '.fc_module.weight'] = _t(rng.uniform(-0.3, 0.3, size=info['n']))
+                    sd[prefix + '.fc_module.bias'] = _t(rng.uniform(-0.3, 0.3, size=info['n']))
+                    sd[prefix + '.fc_module.initialized'] = torch.tensor(1)
+                elif kind == 'fc_imblock':
+                    _imblock_entries(sd, prefix, info, arch, seed, power_iters, sub='.nnet')
     else:
         for j, (kind, info) in enumerate(fc_flow_layout(arch)):
             _imblock_entries(sd, 'chain.%d' % j, info, arch, seed, power_iters)
