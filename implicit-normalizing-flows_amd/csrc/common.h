@@ -84,20 +84,84 @@ __device__ __forceinline__ float elu_fast_d(float a) { return a > 0.f ? 1.f : __
 __device__ __forceinline__ float softplus_fast_f(float a) { return a > 20.f ? a : __logf(1.f + __expf(a)); }
 __device__ __forceinline__ float softplus_fast_d(float a) { return a > 20.f ? 1.f : sigmoid_fast(a); }
 
+// Sin (activations.py:7-12) in a short inline form for the fused kernels (fcnet_h3.hip, fcblock.hip, fused313*.hip): the
+// precise sinf / cosf expand to hundreds of instructions per call.  sin(2 pi a) and cos(2 pi a) together.  The argument
+// is in revolutions, so the reduction r = a - rint(a) is exact (|a| < 2^22); one fold to |r| <= 1/4 (exact), then
+// Taylor polynomials in x = 2 pi r, |x| <= pi/2, through x^13 / x^14 (truncation <= 7e-10): within a few ulp of the
+// correctly rounded values.
+__device__ __forceinline__ void sincos_2pi(float a, float& sn, float& cs) {
+  const float r = a - __builtin_rintf(a);
+  const bool fold = fabsf(r) > 0.25f;
+  const float t = fold ? __builtin_copysignf(0.5f, r) - r : r;
+  const float x = t * TWO_PI_F, x2 = x * x;
+  float ps = -1.f / 6227020800.f;                // sin: x (1 - x^2/3! + ... - x^12/13!)
+  ps = __builtin_fmaf(ps, x2, 1.f / 39916800.f);
+  ps = __builtin_fmaf(ps, x2, -1.f / 362880.f);
+  ps = __builtin_fmaf(ps, x2, 1.f / 5040.f);
+  ps = __builtin_fmaf(ps, x2, -1.f / 120.f);
+  ps = __builtin_fmaf(ps, x2, 1.f / 6.f);
+  ps = __builtin_fmaf(-ps, x2, 1.f);
+  float pc = 1.f / 87178291200.f;                // cos: 1 - x^2/2! + ... + x^14/14!
+  pc = __builtin_fmaf(pc, x2, -1.f / 479001600.f);
+  pc = __builtin_fmaf(pc, x2, 1.f / 3628800.f);
+  pc = __builtin_fmaf(pc, x2, -1.f / 40320.f);
+  pc = __builtin_fmaf(pc, x2, 1.f / 720.f);
+  pc = __builtin_fmaf(pc, x2, -1.f / 24.f);
+  pc = __builtin_fmaf(pc, x2, 0.5f);
+  pc = __builtin_fmaf(-pc, x2, 1.f);
+  sn = x * ps;
+  cs = fold ? -pc : pc;
+}
+__device__ __forceinline__ float sinact_fast_f(float a) {
+  float sn, cs;
+  sincos_2pi(a, sn, cs);
+  return sn * (0.5f / PI_F);
+}
+__device__ __forceinline__ float sinact_fast_d(float a) {
+  float sn, cs;
+  sincos_2pi(a, sn, cs);
+  return cs;
+}
+
 // The fused 3-1-3 kernels' activations other than Swish, by a run-time kind (a kernel-argument field: the switch is
-// wave-uniform): ELU, Softplus in their fast forms, ReLU
+// wave-uniform): Sin, ELU, Softplus in their fast forms, ReLU.  SIN = false leaves the Sin case out: the Swish
+// forward instantiations' halo staging, which no Sin net reaches, keeps the code it had.
+template <bool SIN = true>
 __device__ __forceinline__ float fused_act_f(int act, float a) {
+  if constexpr (SIN) {
+    if (act == ACT_SIN) return sinact_fast_f(a);
+  }
   switch (act) {
     case ACT_ELU: return elu_fast_f(a);
     case ACT_SOFTPLUS: return softplus_fast_f(a);
     default: return relu_f(a);
   }
 }
+template <bool SIN = true>
 __device__ __forceinline__ float fused_act_d(int act, float a) {
+  if constexpr (SIN) {
+    if (act == ACT_SIN) return sinact_fast_d(a);
+  }
   switch (act) {
     case ACT_ELU: return elu_fast_d(a);
     case ACT_SOFTPLUS: return softplus_fast_d(a);
     default: return relu_d(a);
+  }
+}
+// value and derivative behind one switch (the SAVE / EVALSAVE epilogues): Sin's argument is reduced once; the other
+// kinds are the two helpers' own expressions
+__device__ __forceinline__ void fused_act_fd(int act, float a, float& f, float& d) {
+  switch (act) {
+    case ACT_SIN: {
+      float sn, cs;
+      sincos_2pi(a, sn, cs);
+      f = sn * (0.5f / PI_F);
+      d = cs;
+      break;
+    }
+    case ACT_ELU: f = elu_fast_f(a); d = elu_fast_d(a); break;
+    case ACT_SOFTPLUS: f = softplus_fast_f(a); d = softplus_fast_d(a); break;
+    default: f = relu_f(a); d = relu_d(a); break;
   }
 }
 

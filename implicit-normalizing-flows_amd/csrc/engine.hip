@@ -87,11 +87,13 @@ struct WLayer {
 };
 
 // the activations the fused 3-1-3 conv kernels have a form for (fused313*.hip)
-bool fused_act_kind(int act) { return act == ACT_SWISH || act == ACT_ELU || act == ACT_SOFTPLUS || act == ACT_RELU; }
+bool fused_act_kind(int act) {
+  return act == ACT_SWISH || act == ACT_SIN || act == ACT_ELU || act == ACT_SOFTPLUS || act == ACT_RELU;
+}
 
 // Two fused 3-1-3 nets that one pair launch can run: the same hidden width, and both Swish or both of the other fused
 // activations -- the launch picks its instantiation (Swish epilogues reading beta1 / beta2, or the kind switch reading
-// Net313Args::act) once, from the first net.  ELU / Softplus / ReLU mix freely: the kind is a per-net field.
+// Net313Args::act) once, from the first net.  Sin / ELU / Softplus / ReLU mix freely: the kind is a per-net field.
 template <typename Net>
 bool fused_pair(const Net* a, const Net* b) {
   return a->fused && b->fused && a->fhid == b->fhid && (a->L[0].act == ACT_SWISH) == (b->L[0].act == ACT_SWISH);
@@ -318,7 +320,7 @@ Net313Args net313_args(const InfNet* n, const float* in, int B, Bufs& bf, bool v
   memset(&f, 0, sizeof(f));
   f.in = in;
   f.pre_beta = vjp ? nullptr : n->pre_beta;
-  // another fused activation than Swish (ELU / Softplus / ReLU; the eligibility check made all of the net's the same)
+  // another fused activation than Swish (Sin / ELU / Softplus / ReLU; the eligibility check made all of the net's the same)
   f.act = n->L[0].act == ACT_SWISH ? 0 : n->L[0].act;
   f.pre_act = (vjp || n->pre_act == ACT_SWISH) ? 0 : n->pre_act;
   f.A1 = vjp ? n->F1b : n->F1f;
@@ -1647,7 +1649,7 @@ static bool grad_supported(const InfNet* n) {
     if (n->L[l].act != ACT_SWISH && n->L[l].act != ACT_SIN) return false;
   if (n->L.back().act != ACT_NONE) return false;
   if (n->fc && n->pre_act != ACT_NONE) return false;
-  return n->pre_act == ACT_NONE || n->pre_act == ACT_SWISH;
+  return n->pre_act == ACT_NONE || n->pre_act == ACT_SWISH || n->pre_act == ACT_SIN;
 }
 
 static float* grad_out(float* const* arr, int l) { return arr ? arr[l] : nullptr; }
@@ -1793,12 +1795,14 @@ int inf_net_create(const InfNetDesc* desc, InfNet** out) {
   }
   const int L = (int)n->L.size();
   if (L == 0 || n->L.back().act != ACT_NONE) { delete n; return INF_ERR_UNSUPPORTED; }
-  // A leading activation other than Swish is applied by the GEMM loader of the parameter-less family's own
-  // instantiations (gemm.hip EP_ACT_ANY), i.e. where the first layer's activation is of that family too -- every net
-  // ImplicitFlow builds (one activation_fn throughout).  Other mixes are not implemented.
+  // A leading activation other than Swish is applied by the GEMM loader of the instantiations that carry it: a leading
+  // Sin by EP_ACT_SIN's (the first layer's activation is Sin), any other by the parameter-less family's own (gemm.hip
+  // EP_ACT_ANY: the first layer's activation is of that family too) -- every net ImplicitFlow builds (one activation_fn
+  // throughout).  Other mixes are not implemented.
   if (n->pre_act != ACT_NONE && n->pre_act != ACT_SWISH) {
     const int a0 = n->L[0].act;
-    if (n->pre_act == ACT_SIN || a0 == ACT_NONE || a0 == ACT_SWISH || a0 == ACT_SIN) { delete n; return INF_ERR_UNSUPPORTED; }
+    const bool ok = n->pre_act == ACT_SIN ? a0 == ACT_SIN : (a0 != ACT_NONE && a0 != ACT_SWISH && a0 != ACT_SIN);
+    if (!ok) { delete n; return INF_ERR_UNSUPPORTED; }
   }
   n->fc = n->L[0].kind == INF_LAYER_LINEAR;
   if (n->fc) {
@@ -3112,10 +3116,10 @@ int param_grad_core(InfNet* n, const float* x, const float* gout, float* gx, con
     } else if (gx || (n->pre_beta && gr->dpre_beta)) {
       const long ne = (long)B * n->d;
       float* gin = gx ? gx : gb.tmp_in;
-      if (n->pre_beta) {
+      if (n->pre_act != ACT_NONE) {     // a leading Swish (with its beta) or Sin
         INF_TRY(layer_vjp(n, 0, g, gb.ga, B, gb, s));
-        INF_TRY(launch_act_bwd1(gb.ga, x, ACT_SWISH, n->pre_beta, gin, gb.bpart, ne, GRAD_BLOCKS, s));
-        if (gr->dpre_beta) INF_TRY(launch_beta_reduce(gb.bpart, GRAD_BLOCKS, gr->dpre_beta, 0, s));
+        INF_TRY(launch_act_bwd1(gb.ga, x, n->pre_act, n->pre_beta, gin, gb.bpart, ne, GRAD_BLOCKS, s));
+        if (n->pre_beta && gr->dpre_beta) INF_TRY(launch_beta_reduce(gb.bpart, GRAD_BLOCKS, gr->dpre_beta, 0, s));
       } else {
         INF_TRY(layer_vjp(n, 0, g, gin, B, gb, s));
       }
@@ -3155,9 +3159,9 @@ int surrogate_core(InfNet* n, const float* x, const float* w, const float* eps, 
   const long nin = (long)B * n->d;
   // input tangent: eps * preact'(x) (or eps)
   const float* in_tan = eps;
-  if (n->pre_beta) {
+  if (n->pre_act != ACT_NONE) {
     INF_HIP(hipMemcpyAsync(gb.Ad[0], eps, sizeof(float) * nin, hipMemcpyDeviceToDevice, s));
-    INF_TRY(launch_act_tangent(gb.Ad[0], x, ACT_SWISH, n->pre_beta, nin, s));
+    INF_TRY(launch_act_tangent(gb.Ad[0], x, n->pre_act, n->pre_beta, nin, s));
     in_tan = gb.Ad[0];
   }
   // forward: primal pre-activations H, tangents Hd, activation tangents Ad
@@ -3202,11 +3206,11 @@ int surrogate_core(InfNet* n, const float* x, const float* w, const float* eps, 
       G_pri = np;
     } else {
       float* gin = gx ? gx : gb.tmp_in;
-      if (n->pre_beta) {
+      if (n->pre_act != ACT_NONE) {
         // x-gradient: gbar_adot eps s''(x) + gbar_a s'(x); beta: ... (act_bwd2 with h = x, hdot = eps)
-        INF_TRY(launch_act_bwd2(gb.gad, G_pri ? gb.ga : nullptr, x, eps, ACT_SWISH, n->pre_beta, gb.xin, gin, gb.bpart,
+        INF_TRY(launch_act_bwd2(gb.gad, G_pri ? gb.ga : nullptr, x, eps, n->pre_act, n->pre_beta, gb.xin, gin, gb.bpart,
                                 nin, GRAD_BLOCKS, s));
-        if (gr->dpre_beta) INF_TRY(launch_beta_reduce(gb.bpart, GRAD_BLOCKS, gr->dpre_beta, 0, s));
+        if (n->pre_beta && gr->dpre_beta) INF_TRY(launch_beta_reduce(gb.bpart, GRAD_BLOCKS, gr->dpre_beta, 0, s));
       } else if (gx) {
         if (G_pri) INF_HIP(hipMemcpyAsync(gx, gb.ga, sizeof(float) * nin, hipMemcpyDeviceToDevice, s));
         else INF_HIP(hipMemsetAsync(gx, 0, sizeof(float) * nin, s));

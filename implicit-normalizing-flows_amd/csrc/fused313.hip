@@ -183,7 +183,7 @@ __device__ __forceinline__ void net313_body(const Net313Pair& pr) {
   // ---- stage the input halo tile (fused313_stage.h; the forward applies the preact swish, the series chains) ----
   float hmx = 0.f;                                  // this thread's max |staged halo value| (H3AC; dead otherwise)
   double dacc = 0.0;
-  stage_halo<NT, 8, true>(a, hg, tid, vh, hmx, dacc, [](bool) {});
+  stage_halo<NT, 8, true, (MODE == MODE_VJP || ACTK != 0)>(a, hg, tid, vh, hmx, dacc, [](bool) {});
   // per-tile trace partial: wave sums -> a reserved LDS slot at the end of the LDS (never reused)
   double* red = reinterpret_cast<double*>(smem + F_LDS_FLOATS - 16);
   // H3: per-wave column maxima of the phase-B / phase-C operand [NW][F_BN] and the halo maxima [NW] of
@@ -463,8 +463,8 @@ __device__ __forceinline__ void net313_body(const Net313Pair& pr) {
               v = swish_fast_f(z, sp1);
               if constexpr (MODE == MODE_SAVE || MODE == MODE_EVALSAVE) dv[r] = swish_fast_d(z, sp1);
             } else {
-              v = fused_act_f(a.act, z);
-              if constexpr (MODE == MODE_SAVE || MODE == MODE_EVALSAVE) dv[r] = fused_act_d(a.act, z);
+              if constexpr (MODE == MODE_SAVE || MODE == MODE_EVALSAVE) fused_act_fd(a.act, z, v, dv[r]);
+              else v = fused_act_f(a.act, z);
             }
           }
           if constexpr (H3) cm[b] = fmaxf(cm[b], fabsf(v));

@@ -70,7 +70,9 @@ struct HaloGeom {
 //    clamped address issued before any is used.  The values staged do not depend on FU.
 // SIDE_ALWAYS: the side inputs (vmul_x, dot_eps, acc_w) are loaded whether the net has them or not (from a dummy
 // address where it does not), the form the 64-pixel kernels were measured with; false loads them only where present.
-template <int NT, int FU, bool SIDE_ALWAYS, class AfterLoads>
+// SIN: the leading activation / the series-chaining derivative may be Sin (every instantiation but the Swish forward
+// ones, which only Swish nets launch; the VJP instantiations are shared by all kinds).
+template <int NT, int FU, bool SIDE_ALWAYS, bool SIN, class AfterLoads>
 __device__ __forceinline__ void stage_halo(const Net313Args& a, const HaloGeom& g, int tid, float* vh, float& hmx,
                                            double& dacc, AfterLoads&& after_loads) {
   const int C = g.C, H = g.H, W = g.W, P = g.P(), seg = g.seg, rows = g.rows, y0 = g.y0, x0 = g.x0;
@@ -127,7 +129,7 @@ __device__ __forceinline__ void stage_halo(const Net313Args& a, const HaloGeom& 
           const bool vt = y2 >= 0 && y2 < H && x2 >= 0 && x2 < W;
           v += vt ? tv[u][tp] : 0.f;
         }
-        if (mx) v = v * (a.vmul_act ? fused_act_d(a.vmul_act, xm[u]) : swish_fast_d(xm[u], msp));
+        if (mx) v = v * (a.vmul_act ? fused_act_d<SIN>(a.vmul_act, xm[u]) : swish_fast_d(xm[u], msp));
         v = ok ? v : 0.f;
         if (ep && ok == 2) dacc += (double)v * (double)ev[u];
         if (accw && ok == 2) accw[(long)c * P + yy * W + xx] = fmaf(a.acc_coef, v, wv[u]);
@@ -165,7 +167,7 @@ __device__ __forceinline__ void stage_halo(const Net313Args& a, const HaloGeom& 
         if (ok[u]) {
           v = lv[u];
           if (a.pre_beta) v = swish_fast_f(v, pre_sp);
-          else if (a.pre_act) v = fused_act_f(a.pre_act, v);
+          else if (a.pre_act) v = fused_act_f<SIN>(a.pre_act, v);
         }
         hmx = fmaxf(hmx, fabsf(v));
         if (i < vhz) vh[i] = v;

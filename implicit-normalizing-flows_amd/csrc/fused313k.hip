@@ -164,7 +164,7 @@ __global__ __launch_bounds__(512) void net313k_kernel(Net313Pair pr) {
   // ---- stage the input halo tile (fused313_stage.h); the early loads go out after the last pass's loads ----
   float hmx = 0.f;
   double dacc = 0.0;
-  stage_halo<KB_NT, 4, false>(a, hg, tid, vh, hmx, dacc, [&](bool last) {
+  stage_halo<KB_NT, 4, false, (VJP || ACTK != 0)>(a, hg, tid, vh, hmx, dacc, [&](bool last) {
     if (early_pending && last) issue_early();
   });
   put_wave_max(lane, wid, hmx, hmax);
@@ -368,8 +368,14 @@ __global__ __launch_bounds__(512) void net313k_kernel(Net313Pair pr) {
                 va[b][4 * j + q] = swish_fast_f(z, sp1);
                 if constexpr (SAVE) dd[q] = swish_fast_d(z, sp1);
               } else {
-                va[b][4 * j + q] = fused_act_f(a.act, z);
-                if constexpr (SAVE) dd[q] = fused_act_d(a.act, z);
+                if constexpr (SAVE) {
+                  float fv, dv;
+                  fused_act_fd(a.act, z, fv, dv);
+                  va[b][4 * j + q] = fv;
+                  dd[q] = dv;
+                } else {
+                  va[b][4 * j + q] = fused_act_f(a.act, z);
+                }
               }
             }
             if constexpr (SAVE) const_cast<f32x4*>(dptr(a.d1, rbA, b))[j] = dd;
@@ -540,8 +546,13 @@ __global__ __launch_bounds__(512) void net313k_kernel(Net313Pair pr) {
             acc[m][b][r] = swish_fast_f(z, sp2);
             if constexpr (SAVE) dd[r] = swish_fast_d(z, sp2);
           } else {
-            acc[m][b][r] = fused_act_f(a.act, z);
-            if constexpr (SAVE) dd[r] = fused_act_d(a.act, z);
+            if constexpr (SAVE) {
+              float fv;
+              fused_act_fd(a.act, z, fv, dd[r]);
+              acc[m][b][r] = fv;
+            } else {
+              acc[m][b][r] = fused_act_f(a.act, z);
+            }
           }
         }
         if constexpr (SAVE) {

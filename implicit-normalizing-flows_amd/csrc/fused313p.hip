@@ -82,7 +82,7 @@ __global__ __launch_bounds__(PB_NT) __attribute__((amdgpu_waves_per_eu(2))) void
   // ---- stage the input halo tile (fused313_stage.h) ----
   float hmx = 0.f;
   double dacc = 0.0;
-  stage_halo<PB_NT, 4, false>(a, hg, tid, vh, hmx, dacc, [](bool) {});
+  stage_halo<PB_NT, 4, false, true>(a, hg, tid, vh, hmx, dacc, [](bool) {});
   put_wave_max(lane, wid, hmx, hmax);
   put_wave_dot(a, lane, wid, dacc, red);
   fill_koff<PB_NT>(hg, tid, koff);

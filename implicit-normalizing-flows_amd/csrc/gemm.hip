@@ -113,6 +113,11 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_f32_kernel(GemmArgs g) {
             v.x = act_any_f(g.pre_act, v.x); v.y = act_any_f(g.pre_act, v.y);
             v.z = act_any_f(g.pre_act, v.z); v.w = act_any_f(g.pre_act, v.w);
           }
+        } else if constexpr (EPI == EP_ACT_SIN) {   // (a leading Sin: only in front of a Sin layer)
+          if (g.pre_act == ACT_SIN) {
+            v.x = sinact_f(v.x); v.y = sinact_f(v.y);
+            v.z = sinact_f(v.z); v.w = sinact_f(v.w);
+          }
         }
         rb4[i] = v;
       }
@@ -126,6 +131,8 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_f32_kernel(GemmArgs g) {
           if (g.pre_beta) v = swish_f(v, pre_sp);
           else if constexpr (EPI == EP_ACT_ANY) {
             if (g.pre_act != ACT_NONE) v = act_any_f(g.pre_act, v);
+          } else if constexpr (EPI == EP_ACT_SIN) {
+            if (g.pre_act == ACT_SIN) v = sinact_f(v);
           }
         }
         rb1[i] = v;
@@ -144,6 +151,8 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_f32_kernel(GemmArgs g) {
             if (g.pre_beta) v = swish_f(v, pre_sp);
             else if constexpr (EPI == EP_ACT_ANY) {
               if (g.pre_act != ACT_NONE) v = act_any_f(g.pre_act, v);
+            } else if constexpr (EPI == EP_ACT_SIN) {
+              if (g.pre_act == ACT_SIN) v = sinact_f(v);
             }
           }
         }
@@ -428,9 +437,11 @@ int launch_gemm(const GemmArgs& g, int bload, int epi, hipStream_t s) {
     epi = g.act == ACT_SWISH ? EP_ACT_SWISH
                              : (g.act == ACT_SIN ? EP_ACT_SIN : (g.act == ACT_NONE ? EP_ACT_NONE : EP_ACT_ANY));
   if (!g.pre_beta && g.pre_act == ACT_SWISH) return INF_ERR_INVALID;   // a leading Swish comes with its beta
-  // a parameter-less leading activation is applied by the EP_ACT_ANY instantiations' loader only, so that the Swish /
-  // Sin / plain instantiations keep the registers they had (inf_net_create admits no other combination)
-  if (!g.pre_beta && g.pre_act != ACT_NONE && epi != EP_ACT_ANY) return INF_ERR_UNSUPPORTED;
+  // a parameter-less leading activation is applied by the EP_ACT_ANY instantiations' loader only, and a leading Sin by
+  // the EP_ACT_SIN ones', so that the Swish / plain instantiations keep the registers they had (inf_net_create admits
+  // no other combination)
+  if (!g.pre_beta && g.pre_act != ACT_NONE && !(g.pre_act == ACT_SIN ? epi == EP_ACT_SIN : epi == EP_ACT_ANY))
+    return INF_ERR_UNSUPPORTED;
   if (g.Kpad % 16 != 0 || g.M <= 0 || g.N < 0) return INF_ERR_INVALID;
   const bool vec = (bload == BL_DIRECT) && (g.P % 4 == 0) && (g.N % 4 == 0) && (g.x_sample % 4 == 0) &&
                    ((uintptr_t)g.X % 16 == 0);

@@ -427,7 +427,9 @@ def _unsupported(module):
     return HipError('net %s is not supported by the MI355X engine (supported: nn.Sequential of InducedNormConv2d '
                     '(stride 1, k in {1,3}) / InducedNormLinear, with or without bias, and the activations Swish, Sin, '
                     'nn.ELU (alpha 1), nn.Softplus (beta 1, threshold 20), nn.ReLU, LipschitzCube, Identity, Zero; '
-                    'the net must end in a layer, not an activation)' % type(module).__name__)
+                    'the net must end in a layer, not an activation; a leading activation must be of the hidden '
+                    'activations\' family: Swish before Swish, Sin before Sin, one of the others before any of the '
+                    'others)' % type(module).__name__)
 
 
 def native_net(module, shape, device):

@@ -592,14 +592,15 @@ class imBlock(nn.Module):
         return self._finish_logdet(ests[0] - ests[1], n_ps, ns)
 
     def _engine_grads(self, t):
-        """Whether the engine computes the parameter gradients of both nets: conv nets with Swish activations, fc nets
-        (d <= 16) with Swish / Sin; otherwise the training graph keeps autograd on the nets.  (The fc nets' Neumann
-        estimator keeps autograd for its surrogate.)"""
+        """Whether the engine computes the parameter gradients of both nets: conv nets with Swish or Sin activations
+        (a leading one included, preact), fc nets (d <= 16) with Swish / Sin; otherwise the training graph keeps
+        autograd on the nets.  (The fc nets' Neumann estimator keeps autograd for its surrogate.)"""
         if t.dim() not in (2, 4) or (t.dim() == 2 and t.shape[1] > 16):
             return False
         key = '_engine_grads_ok' if t.dim() == 4 else '_engine_grads_ok_fc'
         if key not in self.__dict__:
-            allowed = ('InducedNormConv2d', 'Swish') if t.dim() == 4 else ('InducedNormLinear', 'Swish', 'Sin')
+            allowed = (('InducedNormConv2d', 'Swish', 'Sin') if t.dim() == 4
+                       else ('InducedNormLinear', 'Swish', 'Sin'))
             ok = True
             for net in (self.nnet_x, self.nnet_z):
                 for m in net.modules():

@@ -10,7 +10,7 @@
 
 Weight gradients are with respect to the RAW weights (through the Lipschitz normalisation, like
 autograd through ``compute_weight(update=False)``).  Conv and fc nets with Swish / Sin between layers that all have a
-bias (conv nets may lead with a Swish); other nets return None and the caller keeps autograd.
+bias (conv nets may lead with a Swish or a Sin); other nets return None and the caller keeps autograd.
 """
 import ctypes
 

@@ -78,6 +78,14 @@ CONFIGS['power_elu'] = dict(POWER, act='elu')
 CONFIGS['toy_softplus'] = dict(TOY, act='softplus')
 del _a
 
+# Sin, the default activation of the reference's image driver (train_img.py --act), on the image architectures: with the
+# leading activation of preact (the architectures' own setting) and without.  The fixtures of
+# tests/golden/make_golden_sin.py.
+CONFIGS['cifar10_small_sin'] = dict(CIFAR10_SMALL, act='sin')
+CONFIGS['cifar10_sin'] = dict(CIFAR10, act='sin')
+CONFIGS['cifar10_small_sin_nopre'] = dict(CIFAR10_SMALL, act='sin', preact=False)
+CONFIGS['cifar10_sin_nopre'] = dict(CIFAR10, act='sin', preact=False)
+
 # Mixed induced norms (--vnorms): layer i of every net is bounded in the l_p[i] -> l_p[i+1] norm, 'f' standing for
 # inf.  An arch without the key is all-2.  '13f1' gives 1 -> 3, 3 -> inf and inf -> 1: every normalisation form of
 # csrc/power.hip (one-hot v, power u and v, one-hot u on the 1x1 conv, both sign vectors) on layers that the
@@ -96,6 +104,8 @@ FC_IMG_SMALL = dict(CIFAR10_SMALL, input_size=(3, 8, 8), n_blocks=[1, 1], fc=Tru
 TAB_D43 = dict(POWER, d=43, n_blocks=4)
 TAB_D63 = dict(POWER, d=63, n_blocks=4)
 CONFIGS.update(fcend_small=FCEND_SMALL, fc_img_small=FC_IMG_SMALL, tab_d43=TAB_D43, tab_d63=TAB_D63)
+# fc_end with Sin and preact: the conv block and the two fc blocks (d = 192) all lead with a Sin but the first one's nets
+CONFIGS['fcend_small_sin'] = dict(FCEND_SMALL, act='sin')
 
 
 # Layers of the mixed-norm power-iteration fixtures (make_golden_vnorms.py): the smallest shapes that reach every

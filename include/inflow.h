@@ -362,11 +362,11 @@ int inf_power_iteration_batch(const InfPowerIterDesc* descs, int n, int max_iter
 
 /* ---- parameter gradients (training path) -----------------------------------------------------------
  * Conv and fc nets whose layers all have a bias, with Swish or Sin between the layers, nothing after the last one and,
- * conv nets only, no leading activation or a leading Swish; any other net: INF_ERR_UNSUPPORTED.
+ * conv nets only, no leading activation or a leading Swish / Sin; any other net: INF_ERR_UNSUPPORTED.
  * Device buffers per weight layer l (in order; NULL entries / arrays are skipped): dW[l] the gradient of
  * the RAW weight (through W / max(1, u.(W v) / coeff), mixed_lipschitz.py:378-385), db[l] the bias,
  * dbeta[l] the beta of the swish applied after layer l (NULL for the last layer and after a Sin); dpre_beta the
- * preact swish.  Buffers are overwritten. */
+ * preact swish (a leading Sin has no parameter).  Buffers are overwritten. */
 typedef struct InfNetGrads {
   float** dW;
   float** db;

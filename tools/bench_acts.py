@@ -1,10 +1,11 @@
 """Eval-step time of the CIFAR-10 flow per activation, and of the tabular / toy flows with the fused fc activations.
 
-    python tools/bench_acts.py [--batch 64] [--steps 20] [--warmup 3] [act ...]
+    python tools/bench_acts.py [--batch 64] [--steps 20] [--warmup 3] [--no-fc] [act ...]
     INFLOW_NO_FUSED=1 python tools/bench_acts.py ...      # the same nets on the generic GEMM chain
 
-conv: dict(CIFAR10, act=a) at --batch, one density evaluation per step (image_logpx, device probes as bench.py).  All
-four have fused 3-1-3 kernels; INFLOW_NO_FUSED=1 gives the generic path's time for the fused / generic ratio.
+conv: dict(CIFAR10, act=a) at --batch, one density evaluation per step (image_logpx, device probes as bench.py); act is
+one of swish, sin, elu, softplus, relu, and `<act>_nopre` is the same flow with preact=False (no leading activation).
+All have fused 3-1-3 kernels; INFLOW_NO_FUSED=1 gives the generic path's time for the fused / generic ratio.
 fc: POWER with act in {sin, elu} and TOY with act in {sin, softplus} at B = 10 000 (the fused fc kernels).
 One JSON line per net: ms per step (median and min / max over the steps) and the engine's launch profile of one step.
 """
@@ -59,14 +60,17 @@ def main():
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--fc-batch', type=int, default=10000)
-    ap.add_argument('acts', nargs='*', default=['swish', 'elu', 'softplus', 'relu'])
+    ap.add_argument('--no-fc', action='store_true', help='conv flows only')
+    ap.add_argument('acts', nargs='*', default=['swish', 'sin', 'sin_nopre', 'elu', 'softplus', 'relu'])
     args = ap.parse_args()
     set_probe_mode('device', seed=0)
     for a in args.acts:
         x = syn.image_batch(args.batch, seed=0).cuda()
-        time_net('cifar10_' + a, dict(syn.CIFAR10, act=a), x, args.steps, args.warmup)
+        nopre = a.endswith('_nopre')
+        arch = dict(syn.CIFAR10, act=a[:-len('_nopre')] if nopre else a, preact=not nopre)
+        time_net('cifar10_' + a, arch, x, args.steps, args.warmup)
     for base, name, a in ((syn.POWER, 'power', 'sin'), (syn.POWER, 'power', 'elu'), (syn.TOY, 'toy', 'sin'),
-                          (syn.TOY, 'toy', 'softplus')):
+                          (syn.TOY, 'toy', 'softplus')) if not args.no_fc else ():
         x = syn.tabular_batch(args.fc_batch, base['d'], seed=0).cuda()
         time_net('%s_%s' % (name, a), dict(base, act=a), x, args.steps, args.warmup)
 
