@@ -157,6 +157,7 @@ struct InfNet {
   int presplit = 1;        // INF_OPT_FUSED_PRESPLIT
   int fc_block = 1;        // INF_OPT_FC_BLOCK (read on net_z of inf_imblock_eval_exact)
   int fc_series = 1;       // INF_OPT_FC_SERIES (read on the first net of inf_logdet_series[_pair])
+  int fc_skinny = 1;       // INF_OPT_FC_SKINNY (fc nets over more than FC_NARROW_MAX features: layer_gemm)
   // fused fc path (fcnet.hip): the whole net in one launch per evaluation (forward and forward-mode Jacobian)
   bool fcfused = false;
   // f16x3 planes of the fused fc layers (fcnet_h3.hip, filled at refresh): layer l at fch + fch_off[l], exponent fchexp[l]
@@ -215,6 +216,9 @@ struct Bufs {
   // (OutArgs::stop_ev) when its launcher can, which sets stop_bound; enqueue_sumsq then records no marker after it
   hipEvent_t stop_ev = nullptr;
   bool stop_bound = false;
+  // wide fc nets: the split-K partials of launch_gemm_skinny (written and read within one layer's two launches)
+  float* kslab = nullptr;
+  size_t kslab_bytes = 0;
   bool sample_sums = false;   // conv residuals write each sample's total into bf.part (the readback slot; broyden_core)
 };
 
@@ -272,6 +276,9 @@ size_t carve(const InfNet* n, int B, int T, void* ws, size_t cap, Bufs& b) {
     b.bk_out = nullptr;
     b.bk_sync_bytes = b.bk_out_bytes = 0;
   }
+  // (carved whatever INF_OPT_FC_SKINNY says: a workspace sized before the option changes stays large enough)
+  b.kslab_bytes = (n->fc && n->d > FC_NARROW_MAX) ? SKINNY_SLAB_BYTES : 0;
+  b.kslab = b.kslab_bytes ? w.take<float>(b.kslab_bytes / sizeof(float)) : nullptr;
   return w.off + 256;
 }
 
@@ -311,6 +318,17 @@ GemmArgs gemm_base(const InfNet* n, const Operand& op, const float* X, int in_ch
 void set_out(const InfNet* n, GemmArgs& g, float* out, int out_rows) {
   g.out = out;
   g.o_sample = n->fc ? 0 : (long)out_rows * n->P;
+}
+
+// Every per-layer GEMM of the unfused chains (forward, VJP, gradient chain).  The layers of an fc net over more than
+// FC_NARROW_MAX features take the skinny family (gemm_skinny.hip: (d, B) tensors have N = B columns, which leaves
+// launch_gemm's 128 x 128 tile 1 - 24 workgroups) unless INF_OPT_FC_SKINNY is 0 or N alone gives the 128 x 128 tiling a
+// workgroup per CU (256); everything else -- conv nets, narrow fc nets -- calls launch_gemm exactly as before.
+int layer_gemm(const InfNet* n, const GemmArgs& g, int load, int epi, float* kslab, size_t kslab_bytes, hipStream_t s) {
+  if (n->fc && n->d > FC_NARROW_MAX && n->fc_skinny && load == BL_DIRECT && epi != EP_BIAS_PRIMAL &&
+      (long)((g.M + 127) / 128) * ((g.N + 127) / 128) < 256)
+    return launch_gemm_skinny(g, epi, kslab, kslab_bytes, s);
+  return launch_gemm(g, load, epi, s);
 }
 
 // Forward chain.  mode = OM_* for the output stage, or -1 for "save derivatives only" (log-det prep:
@@ -418,7 +436,7 @@ int run_forward(InfNet* n, const float* x, int B, Bufs& bf, int mode, const OutA
     g.act_beta = w.act_beta;
     g.deriv_out = (mode < 0) ? bf.D[l] : nullptr;
     g.write_out = (mode < 0 && l == L - 2) ? 0 : 1;
-    INF_TRY(launch_gemm(g, w.f.load, EP_BIAS_ACT, s));
+    INF_TRY(layer_gemm(n, g, w.f.load, EP_BIAS_ACT, bf.kslab, bf.kslab_bytes, s));
     cur = out;
     cur_ch = w.cout;
   }
@@ -428,7 +446,7 @@ int run_forward(InfNet* n, const float* x, int B, Bufs& bf, int mode, const OutA
   g.pre_beta = (L == 1) ? n->pre_beta : nullptr;
   g.pre_act = (L == 1) ? n->pre_act : ACT_NONE;
   set_out(n, g, bf.Y, w.f.M);
-  INF_TRY(launch_gemm(g, w.f.load, EP_STORE, s));
+  INF_TRY(layer_gemm(n, g, w.f.load, EP_STORE, bf.kslab, bf.kslab_bytes, s));
   OutArgs a = *oa;
   a.Y = bf.Y;
   a.y_sample = n->fc ? 0 : (long)w.f.M * n->P;
@@ -476,14 +494,14 @@ int run_vjp(InfNet* n, const float* v, float* vout, const float* xin, const floa
     GemmArgs g = gemm_base(n, w.g, cur, cur_ch, B);
     set_out(n, g, out, w.cin);
     g.deriv_in = bf.D[l - 1];
-    INF_TRY(launch_gemm(g, w.g.load, EP_MUL_DERIV, s));
+    INF_TRY(layer_gemm(n, g, w.g.load, EP_MUL_DERIV, bf.kslab, bf.kslab_bytes, s));
     cur = out;
     cur_ch = w.cin;
   }
   const WLayer& w = n->L[0];
   GemmArgs g = gemm_base(n, w.g, cur, cur_ch, B);
   set_out(n, g, bf.Y, w.g.M);
-  INF_TRY(launch_gemm(g, w.g.load, EP_STORE, s));
+  INF_TRY(layer_gemm(n, g, w.g.load, EP_STORE, bf.kslab, bf.kslab_bytes, s));
   OutArgs a;
   memset(&a, 0, sizeof(a));
   a.Y = bf.Y;
@@ -1507,6 +1525,8 @@ struct GradBufs {
   float *x_t, *w_t, *e_t, *gx_t;     // fc nets: the internal-layout (d, N) copies of the boundary inputs / x-gradient
   double *bpart, *dot;
   int max_split;
+  float* kslab;          // wide fc nets: launch_gemm_skinny's split-K partials (Bufs::kslab)
+  size_t kslab_bytes;
 };
 constexpr int GRAD_SPLIT = 32;
 constexpr int GRAD_BLOCKS = 512;
@@ -1538,6 +1558,8 @@ size_t carve_grad(const InfNet* n, int B, void* ws, size_t cap, GradBufs& g) {
   g.bpart = w.take<double>(std::max<size_t>(GRAD_BLOCKS + 64, glue_batched_dot_scratch(B, (long)n->hidden_max * n->P) + 64));
   g.dot = w.take<double>(128);      // [0] the dot, [1..64] its block partials
   g.max_split = GRAD_SPLIT;
+  g.kslab_bytes = (n->fc && n->d > FC_NARROW_MAX) ? SKINNY_SLAB_BYTES : 0;
+  g.kslab = g.kslab_bytes ? w.take<float>(g.kslab_bytes / sizeof(float)) : nullptr;
   return w.off + 256;
 }
 
@@ -1559,13 +1581,13 @@ static int layer_input(InfNet* n, int l, const float* x, GradBufs& gb, int B, hi
 
 // h_l = W_l * in (+ b_l); in gets swish(., pre_beta) on load when pre_beta is set.  l < L-1 (no taps).
 static int layer_fwd(InfNet* n, int l, const float* in, const float* pre_beta, bool bias, float* out, int B,
-                     hipStream_t s) {
+                     GradBufs& gb, hipStream_t s) {
   const WLayer& w = n->L[l];
   GemmArgs g = gemm_base(n, w.f, in, w.cin, B);
   g.pre_beta = pre_beta;
   set_out(n, g, out, w.cout);
   g.bias = bias ? w.b : nullptr;
-  return launch_gemm(g, w.f.load, bias ? EP_BIAS : EP_STORE, s);
+  return layer_gemm(n, g, w.f.load, bias ? EP_BIAS : EP_STORE, gb.kslab, gb.kslab_bytes, s);
 }
 
 // out = W_l^T gout  (input-side gradient of layer l, no activation factor)
@@ -1588,7 +1610,7 @@ static int layer_vjp(InfNet* n, int l, const float* gout, float* out, int B, Gra
     return launch_conv_out(a, B, s);
   }
   set_out(n, g, out, w.cin);
-  return launch_gemm(g, w.g.load, EP_STORE, s);
+  return layer_gemm(n, g, w.g.load, EP_STORE, gb.kslab, gb.kslab_bytes, s);
 }
 
 // dW_eff of layer l = sum_{b,p} G (x) X~ (accumulate: add into gb.dWe), X = in_l
@@ -3097,7 +3119,7 @@ int param_grad_core(InfNet* n, const float* x, const float* gout, float* gx, con
   std::vector<const float*> Ain(L, nullptr);
   for (int l = 0; l < L; ++l) {
     INF_TRY(layer_input(n, l, x, gb, B, s, &Ain[l]));
-    if (l + 1 < L) INF_TRY(layer_fwd(n, l, Ain[l], nullptr, true, gb.H[l], B, s));
+    if (l + 1 < L) INF_TRY(layer_fwd(n, l, Ain[l], nullptr, true, gb.H[l], B, gb, s));
   }
   // backward
   const float* g = gout;
@@ -3168,9 +3190,9 @@ int surrogate_core(InfNet* n, const float* x, const float* w, const float* eps, 
   std::vector<const float*> Ain(L, nullptr);     // each layer's input activated once (gb.A)
   for (int l = 0; l + 1 < L; ++l) {
     INF_TRY(layer_input(n, l, x, gb, B, s, &Ain[l]));
-    INF_TRY(layer_fwd(n, l, Ain[l], nullptr, true, gb.H[l], B, s));
+    INF_TRY(layer_fwd(n, l, Ain[l], nullptr, true, gb.H[l], B, gb, s));
     const float* tin = l == 0 ? in_tan : gb.Ad[l];
-    INF_TRY(layer_fwd(n, l, tin, nullptr, false, gb.Hd[l], B, s));
+    INF_TRY(layer_fwd(n, l, tin, nullptr, false, gb.Hd[l], B, gb, s));
     const long ne = (long)B * n->L[l].cout * n->P;
     INF_HIP(hipMemcpyAsync(gb.Ad[l + 1], gb.Hd[l], sizeof(float) * ne, hipMemcpyDeviceToDevice, s));
     INF_TRY(launch_act_tangent(gb.Ad[l + 1], gb.H[l], n->L[l].act, n->L[l].act_beta, ne, s));
@@ -3366,6 +3388,7 @@ int inf_net_set_option(InfNet* n, int option, int value) {
     case INF_OPT_K128_EXACT_SCALE: slot = &n->exact_scale; hi = 1; break;
     case INF_OPT_FC_BLOCK: slot = &n->fc_block; hi = 2; break;
     case INF_OPT_FC_SERIES: slot = &n->fc_series; hi = 1; break;
+    case INF_OPT_FC_SKINNY: slot = &n->fc_skinny; hi = 1; break;
     case INF_OPT_FUSED_PRESPLIT: slot = &n->presplit; hi = 1; break;
     default: return -INF_ERR_INVALID;
   }
@@ -3387,6 +3410,7 @@ int inf_net_get_option(const InfNet* n, int option) {
     case INF_OPT_K128_EXACT_SCALE: return n->exact_scale;
     case INF_OPT_FC_BLOCK: return n->fc_block;
     case INF_OPT_FC_SERIES: return n->fc_series;
+    case INF_OPT_FC_SKINNY: return n->fc_skinny;
     case INF_OPT_FUSED_PRESPLIT: return n->presplit;
     default: return -INF_ERR_INVALID;
   }

@@ -39,6 +39,14 @@ struct GemmArgs {
 };
 int launch_gemm(const GemmArgs& g, int bload, int epi, hipStream_t s);
 
+// The same contraction for the layers of wide fc nets (gemm_skinny.hip): DIRECT loader with P = N = B and no sample
+// strides, every epilogue but EP_BIAS_PRIMAL, exact fp32 MFMA whatever g.x6 says.  Tiles of 32 x 32 .. 64 x 64; where those
+// leave the part idle and K is deep, S slices of K write fp32 partials to `slab` and a second launch sums them in slice
+// order in fp64 and applies the epilogue (tags 960 partial, 961 reduce, 962 unsplit).  slab may be null (never splits).
+constexpr size_t SKINNY_SLAB_BYTES = 512u << 10;   // the workspace region the engine carves for the partials
+int gemm_skinny_slices(int M, int N, int Ktot, int Kpad, size_t slab_bytes, int* tps_out);
+int launch_gemm_skinny(const GemmArgs& g, int epi, float* slab, size_t slab_bytes, hipStream_t s);
+
 // ------------------------------------------------------------------------------------------
 // Output stage of a conv net whose last layer produced packed taps Y[b][c*9+t][p] (ks = 3) or
 // plain rows Y[b][c][p] (ks = 1): s = sum_t Y[..][shift_t(p)], then a fused epilogue.

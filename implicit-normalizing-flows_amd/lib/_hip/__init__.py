@@ -23,6 +23,7 @@ INF_ACT_ELU, INF_ACT_SOFTPLUS, INF_ACT_RELU, INF_ACT_LCUBE, INF_ACT_IDENTITY, IN
 INF_ERR_UNSUPPORTED = 4       # InfStatus (include/inflow.h)
 INF_OPT_FUSED_K128, INF_OPT_EVAL_OVERLAP, INF_OPT_CONVERGENCE, INF_OPT_K128_EXACT_SCALE = 1, 2, 3, 4   # InfNetOption
 INF_OPT_FC_BLOCK, INF_OPT_FC_SERIES, INF_OPT_LINE_SEARCH, INF_OPT_FUSED_PRESPLIT = 5, 6, 7, 8
+INF_OPT_FC_SKINNY = 9         # wide fc nets' layers on the skinny GEMM family (gemm_skinny.hip); 0: the generic GEMM
 INF_CONV_GLOBAL, INF_CONV_PER_SAMPLE = 0, 1                                # InfConvergence
 CONVERGENCE = {'global': INF_CONV_GLOBAL, 'per_sample': INF_CONV_PER_SAMPLE}
 
@@ -525,6 +526,8 @@ def tag_name(tag):
         return 'fcseries_kernel'
     if tag in WGRAD_TAGS:
         return WGRAD_TAGS[tag]
+    if 960 <= tag <= 962:    # per-layer GEMMs of fc nets wider than 32 features (gemm_skinny.hip)
+        return ['gemm_skinny_kernel<split-K partial>', 'gemm_skinny_reduce_kernel', 'gemm_skinny_kernel<small tile>'][tag - 960]
     if 950 <= tag <= 955:    # output stage of fc nets wider than 32 features (pointwise.hip), 95<mode>
         return 'fc_out_wide_kernel<%s>' % ['PLAIN', 'EMBED', 'RESID', 'RECOMP', 'VJP', 'VJPRES'][tag - 950]
     if 800 <= tag < 900:     # tiled weight-gradient kernel (grad.hip), 8<TMW><TNW>

@@ -176,6 +176,14 @@ int inf_net_get_mfma(const InfNet* net);
  *                         8x8 scale) splits each phase's B operand into its fp16 (h, l) planes once, in LDS, where it is
  *                         produced (phase A's im2col after the halo staging, phases B and C in the epilogues before
  *                         them); 0 splits it per consuming wave, as before round 6.  Bitwise the same results.
+ *   INF_OPT_FC_SKINNY     fc nets over more than 32 features: 1 (default) runs every layer's
+ *                         GEMM of the forward, VJP and gradient chains on the skinny family (gemm_skinny.hip: 32 x 32 ..
+ *                         64 x 64 tiles in exact fp32 MFMA whatever the MFMA mode; deep layers with few outputs split K
+ *                         into slices whose fp32 partials a second launch sums in slice order in fp64),
+ *                         except where the batch alone gives the generic 128 x 128 tiling a workgroup per CU; 0 runs every
+ *                         layer on the generic GEMM, as before round 13.  The workspace does not depend on the value.
+ *                         Other nets ignore it.  Results agree to fp32 roundoff between the values.  It has no environment
+ *                         variable: inf_net_set_option is the one way to change it.
  * Unknown values of INFLOW_FUSED_K128 (0-3), INFLOW_FC_BLOCK (0/1/2), INFLOW_EVAL_OVERLAP / INFLOW_FC_SERIES (0/1) and INFLOW_CONVERGENCE (global/per_sample)
  * make inf_net_create fail with INF_ERR_INVALID.
  * FUSED_K128, EVAL_OVERLAP and K128_EXACT_SCALE are performance / test knobs without a reference counterpart (the reference
@@ -183,7 +191,8 @@ int inf_net_get_mfma(const InfNet* net);
  * agree to fp32 roundoff across their values. */
 typedef enum InfNetOption {
   INF_OPT_FUSED_K128 = 1, INF_OPT_EVAL_OVERLAP = 2, INF_OPT_CONVERGENCE = 3, INF_OPT_K128_EXACT_SCALE = 4,
-  INF_OPT_FC_BLOCK = 5, INF_OPT_FC_SERIES = 6, INF_OPT_LINE_SEARCH = 7, INF_OPT_FUSED_PRESPLIT = 8
+  INF_OPT_FC_BLOCK = 5, INF_OPT_FC_SERIES = 6, INF_OPT_LINE_SEARCH = 7, INF_OPT_FUSED_PRESPLIT = 8,
+  INF_OPT_FC_SKINNY = 9
 } InfNetOption;
 typedef enum InfConvergence { INF_CONV_GLOBAL = 0, INF_CONV_PER_SAMPLE = 1 } InfConvergence;
 int inf_net_set_option(InfNet* net, int option, int value);

@@ -1,6 +1,9 @@
-"""Eval-step time of the flows with fully connected blocks over more than 32 features (DESIGN.md §17).
+"""Eval-step time of the flows with fully connected blocks over more than 32 features (DESIGN.md §17, §19).
 
-    python tools/bench_widefc.py [--steps 20] [--warmup 3] [--out profiles/r11/bench_widefc.jsonl]
+    python tools/bench_widefc.py [--steps 20] [--warmup 3] [--fc-skinny 0] [--out profiles/r13/widefc_new_1.jsonl]
+
+(INFLOW_LIB=<another build's libinflow.so> times that library; --fc-skinny 0 sets INF_OPT_FC_SKINNY to 0 on every engine
+net of the flow after its first evaluation has created them, i.e. the generic GEMM chain on this build: §19's A/B.)
 
   * the CIFAR-10 architecture of run_cifar10.sh (idim 512, n_blocks [2, 2, 2], swish, B = 64) with ``--fc-end True``
     (two fc blocks over the flattened last scale, d = 3072, fc_idim 128) beside the same flow with fc_end False;
@@ -28,7 +31,7 @@ FLOWS = [('cifar10_fc_end', dict(syn.CIFAR10, fc_end=True, fc_idim=128), 64), ('
          ('tab_d43', syn.TAB_D43, 1000), ('tab_d63', syn.TAB_D63, 1000)]
 
 
-def time_flow(name, arch, B, steps, warmup):
+def time_flow(name, arch, B, steps, warmup, fc_skinny=None):
     m = build_flow(arch, B)
     m.load_state_dict(syn.make_state_dict(arch, 0, power_iters=5), strict=True)
     m = m.cuda().eval()
@@ -38,6 +41,13 @@ def time_flow(name, arch, B, steps, warmup):
     else:
         x = syn.tabular_batch(B, arch['d'], seed=0).cuda()
         run = lambda: tabular_logpx(m, x)
+    if fc_skinny is not None:
+        run()                                           # creates the engine nets
+        for mod in m.modules():
+            cache = mod.__dict__.get('_inf_native')
+            for n in (cache.values() if isinstance(cache, dict) else ()):
+                if isinstance(n, _hip.NativeNet):
+                    n.set_option(_hip.INF_OPT_FC_SKINNY, fc_skinny)
     for _ in range(warmup):
         run()
     torch.cuda.synchronize()
@@ -70,11 +80,12 @@ def main():
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--out', default=None)
+    ap.add_argument('--fc-skinny', type=int, default=None, choices=[0, 1])
     args = ap.parse_args()
     set_probe_mode('device', seed=0)
     lines = []
     for name, arch, B in FLOWS:
-        line = json.dumps(time_flow(name, arch, B, args.steps, args.warmup))
+        line = json.dumps(time_flow(name, arch, B, args.steps, args.warmup, args.fc_skinny))
         print(line, flush=True)
         lines.append(line)
     if args.out:
