@@ -65,8 +65,8 @@ def test_kernel_sources_read_no_tuning_environment():
         src = open(os.path.join(csrc, f)).read()
         names |= set(re.findall(r'getenv\("([A-Z0-9_]+)"\)', src))
         assert not re.search(r'#\s*ifdef\s+INFLOW_', src), f
-        if f == 'engine.hip':   # the option defaults are parsed from a table of names
-            names |= {n for n in re.findall(r'"(INFLOW_[A-Z0-9_]+)"', src)}
+        # the option defaults are parsed from a table of names
+        names |= {n for n in re.findall(r'"(INFLOW_[A-Z0-9_]+)"', src)}
     assert names - allowed <= {'INFLOW_FUSED_K128', 'INFLOW_EVAL_OVERLAP', 'INFLOW_CONVERGENCE', 'INFLOW_FC_BLOCK',
                               'INFLOW_FC_SERIES', 'INFLOW_FUSED_PRESPLIT'}, names
 
