@@ -113,6 +113,7 @@ int layer_wgrad(InfNet* n, int l, const float* G, const float* X, const float* x
   a.slab = gb.slab;
   a.out = out;
   a.max_split = gb.max_split;
+  a.fc = n->fc ? 1 : 0;              // (rows, columns) matrices: grad.hip wgrad_fc_kernel
   return launch_wgrad(a, s);
 }
 
@@ -298,8 +299,11 @@ int surrogate_core(InfNet* n, const float* x, const float* w, const float* eps, 
 }
 
 // ---- the log-det estimators' gradients for fc nets (the training path of train_tabular.py / train_toy.py) -----------
+constexpr int FC_JAC_MAX = 16;     // widest fc net with an explicit per-sample Jacobian (fc_jacobian, logdet_pairs_kernel)
+
+// b_scr: the wide series' forward-tangent chain (n_terms + 1, d, B); d <= FC_JAC_MAX takes nothing for it
 size_t logdet_grad_layout(InfNet* n, int B, int mode, int n_terms, char* ws, size_t cap, Bufs* bf, GradBufs* gb,
-                          float** A, float** bv, float** xr, float** gxs, float** eps_t, float** a_scr) {
+                          float** A, float** bv, float** xr, float** gxs, float** eps_t, float** a_scr, float** b_scr) {
   const int T = mode == LOGDET_SERIES ? n_terms : n->d;
   const long N = (long)T * B;
   Bufs bf0;
@@ -309,9 +313,11 @@ size_t logdet_grad_layout(InfNet* n, int B, int mode, int n_terms, char* ws, siz
   const size_t s2 = (carve_grad(n, (int)N, w2, ws ? (cap > s1 ? cap - s1 : 0) : 0, gb ? *gb : gb0) + 255) & ~(size_t)255;
   WS w{ws ? ws + s1 + s2 : nullptr, ws ? (cap > s1 + s2 ? cap - s1 - s2 : 0) : 0, 0};
   float* p[6];
-  const size_t cnt[6] = {(size_t)n->d * N, (size_t)n->d * N, (size_t)n->d * N, (size_t)n->d * N, (size_t)n->d * B,
-                         mode == LOGDET_SERIES ? (size_t)n_terms * n->d * B : 1};
+  // (eps_t: the Jacobian route's transposed probes; the wide route transposes them straight into a_scr)
+  const size_t cnt[6] = {(size_t)n->d * N, (size_t)n->d * N, (size_t)n->d * N, (size_t)n->d * N,
+                         n->d > FC_JAC_MAX ? 0 : (size_t)n->d * B, mode == LOGDET_SERIES ? (size_t)n_terms * n->d * B : 1};
   for (int i = 0; i < 6; ++i) p[i] = w.take<float>(cnt[i]);
+  float* pb = n->d > FC_JAC_MAX ? w.take<float>(((size_t)n_terms + 1) * n->d * B) : nullptr;
   if (A) {
     *A = p[0];
     *bv = p[1];
@@ -319,8 +325,45 @@ size_t logdet_grad_layout(InfNet* n, int B, int mode, int n_terms, char* ws, siz
     *gxs = p[3];
     *eps_t = p[4];
     *a_scr = p[5];
+    *b_scr = pb;
   }
   return s1 + s2 + w.off + 256;
+}
+
+// v -> J(x) v on internal-layout tensors: the forward-tangent chain on the per-layer GEMMs, the hidden layers' tangents
+// scaled by the activation derivatives run_forward(mode = -1) saved at x (bf.D), the last layer stored into out
+int run_jvp(InfNet* n, const float* v, float* out, int B, Bufs& bf, hipStream_t s) {
+  const int L = (int)n->L.size();
+  const float* cur = v;
+  for (int l = 0; l < L; ++l) {
+    const WLayer& w = n->L[l];
+    const bool last = l == L - 1;
+    float* o = last ? out : ((l % 2 == 0) ? bf.h0 : bf.h1);
+    GemmArgs g = gemm_base(n, w.f, cur, w.cin, B);
+    set_out(n, g, o, w.cout);
+    g.deriv_in = last ? nullptr : bf.D[l];
+    INF_TRY(layer_gemm(n, g, w.f.load, last ? EP_STORE : EP_MUL_DERIV, bf.kslab, bf.kslab_bytes, s));
+    cur = o;
+  }
+  return INF_OK;
+}
+
+// The series' pairs without a Jacobian (fc nets wider than FC_JAC_MAX): a_j = (J^T)^j eps by the VJP chain the series
+// value runs (a_scr, j < n), b_m = J^m eps by the forward-tangent chain (b_scr, m <= n: b_n only enters the value), then
+// series_pairs_wide_kernel stacks A, bv, xr over the n B columns and writes the value.  Leaves x internal in bf.xin.
+int series_pairs_chains(InfNet* n, const float* x, const float* eps, const float* coeff, int n_terms, const float* gout,
+                        float* value, int B, Bufs& bf, float* A, float* bv, float* xr, float* a_scr, float* b_scr,
+                        hipStream_t s) {
+  const size_t dB = (size_t)n->d * B;
+  const float* xi;
+  INF_TRY(to_internal(n, x, bf.xin, B, s, &xi));
+  INF_TRY(launch_transpose(eps, a_scr, B, n->d, s));
+  INF_HIP(hipMemcpyAsync(b_scr, a_scr, sizeof(float) * dB, hipMemcpyDeviceToDevice, s));
+  INF_TRY(run_forward(n, xi, B, bf, -1, nullptr, s));
+  for (int j = 0; j + 1 < n_terms; ++j)
+    INF_TRY(run_vjp(n, a_scr + j * dB, a_scr + (j + 1) * dB, xi, nullptr, nullptr, B, bf, s));
+  for (int m = 0; m < n_terms; ++m) INF_TRY(run_jvp(n, b_scr + m * dB, b_scr + (m + 1) * dB, B, bf, s));
+  return launch_series_pairs_wide(a_scr, b_scr, xi, gout, coeff, n_terms, n->d, B, A, bv, xr, value, s);
 }
 
 }  // namespace
@@ -373,35 +416,43 @@ int inf_net_surrogate_grad(InfNet* n, const float* x, const float* w, const floa
 size_t inf_logdet_grad_workspace_bytes(InfNet* n, int B, int mode, int n_terms) {
   if (!n || B <= 0 || mode < LOGDET_SERIES || mode > LOGDET_TRACE || (mode != LOGDET_EXACT && n_terms < 1)) return 0;
   return logdet_grad_layout(n, B, mode, n_terms, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                            nullptr, nullptr);
+                            nullptr, nullptr, nullptr);
 }
 
 // g . S(x) differentiated into every parameter of an fc net and into x, S_b one of the log-det estimators of a sample
-// (mode INF_LOGDET_SERIES / EXACT / TRACE, pointwise.hip logdet_pairs_kernel): the Jacobian per sample (fc_jacobian),
-// the estimator's bilinear pairs at x, then one forward-over-reverse pass over the T B stacked pairs (surrogate_core:
-// the GEMM chains of the generic path, N = T B columns), the x-gradient summed over each sample's pairs.
+// (mode INF_LOGDET_SERIES / EXACT / TRACE): the estimator's bilinear pairs at x, then one forward-over-reverse pass over
+// the T B stacked pairs (surrogate_core: the GEMM chains of the generic path, N = T B columns), the x-gradient summed
+// over each sample's pairs.  d <= 16: the pairs from the Jacobian per sample (fc_jacobian, pointwise.hip
+// logdet_pairs_kernel).  Wider nets, the series only: from the VJP and forward-tangent chains (series_pairs_chains); the
+// exact log-det and the exact trace need the Jacobian and stay INF_ERR_UNSUPPORTED.
 int inf_logdet_grad(InfNet* n, const float* x, int mode, const float* eps, const float* coeff, int n_terms,
                     const float* gout, float* value, float* gx, const InfNetGrads* gr, int B, void* ws, size_t ws_bytes,
                     void* stream) {
   if (!n || !x || !gr || B <= 0 || mode < LOGDET_SERIES || mode > LOGDET_TRACE) return INF_ERR_INVALID;
   if (mode == LOGDET_SERIES && (!eps || !coeff || n_terms < 1 || n_terms > 128)) return INF_ERR_INVALID;
   if (mode == LOGDET_TRACE && (!coeff || n_terms < 1 || n_terms > 128)) return INF_ERR_INVALID;
-  if (!n->fc || n->d > 16 || !grad_supported(n)) return INF_ERR_UNSUPPORTED;
+  const bool wide = n->fc && n->d > FC_JAC_MAX;
+  if (!n->fc || (wide && mode != LOGDET_SERIES) || !grad_supported(n)) return INF_ERR_UNSUPPORTED;
+  if (wide && (long)n_terms * B > 0x7fffffffL) return INF_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
   Bufs bf;
   GradBufs gb;
-  float *A, *bv, *xr, *gxs, *eps_t, *a_scr;
+  float *A, *bv, *xr, *gxs, *eps_t, *a_scr, *b_scr;
   const int nt = mode == LOGDET_EXACT ? 1 : n_terms;
   if (!ws || logdet_grad_layout(n, B, mode, nt, reinterpret_cast<char*>(ws), ws_bytes, &bf, &gb, &A, &bv, &xr, &gxs,
-                                &eps_t, &a_scr) > ws_bytes)
+                                &eps_t, &a_scr, &b_scr) > ws_bytes)
     return INF_ERR_WORKSPACE;
   const int T = mode == LOGDET_SERIES ? n_terms : n->d;
-  const float* tang = nullptr;
-  INF_TRY(fc_jacobian(n, x, B, bf, &tang, s));                     // also leaves x internal in bf.xin
-  if (mode == LOGDET_SERIES) INF_TRY(launch_transpose(eps, eps_t, B, n->d, s));
-  const float one = 1.f;
-  INF_TRY(launch_logdet_pairs(mode, tang, eps_t, bf.xin, gout, mode == LOGDET_EXACT ? &one : coeff, nt, n->d, B, A, bv,
-                              xr, value, a_scr, s));
+  if (wide) {
+    INF_TRY(series_pairs_chains(n, x, eps, coeff, n_terms, gout, value, B, bf, A, bv, xr, a_scr, b_scr, s));
+  } else {
+    const float* tang = nullptr;
+    INF_TRY(fc_jacobian(n, x, B, bf, &tang, s));                     // also leaves x internal in bf.xin
+    if (mode == LOGDET_SERIES) INF_TRY(launch_transpose(eps, eps_t, B, n->d, s));
+    const float one = 1.f;
+    INF_TRY(launch_logdet_pairs(mode, tang, eps_t, bf.xin, gout, mode == LOGDET_EXACT ? &one : coeff, nt, n->d, B, A,
+                                bv, xr, value, a_scr, s));
+  }
   INF_TRY(surrogate_core(n, xr, A, bv, nullptr, gx ? gxs : nullptr, gr, T * B, gb, s));
   if (gx) INF_TRY(launch_sum_pairs(gxs, T, n->d, B, gx, s));
   return INF_OK;

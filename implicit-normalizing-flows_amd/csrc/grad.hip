@@ -199,6 +199,63 @@ __global__ __launch_bounds__(256) void wgrad_tiled_kernel(WgradArgs a) {
       }
 }
 
+// The fc layout (WgradArgs::fc): dW = G X^T with G (M, P) and X (N, P) plain row-major matrices, P the column count
+// (samples, or the stacked pairs of a log-det gradient).  No image / pixel / tap index exists, so a staged element is
+// one load at row * P + column; rows need no alignment (4-byte loads, a wave reads two rows' 32 consecutive columns) and
+// the ragged last chunk is masked by column < P, not padded in memory.  64 x 64 output tile, 4 waves of one 32 x 32
+// exact-fp32 MFMA tile each, 32-column chunks split over blockIdx.z into the slab; the next chunk's operands are loaded
+// into registers while the current chunk's MFMAs run.  The weight matrices of these nets are a few tiles, so the launch
+// wants its parallelism from the split: launch_wgrad gives every split as few chunks as the slab allows.
+__global__ __launch_bounds__(256) void wgrad_fc_kernel(WgradArgs a) {
+  static_assert(WG_K == 32 && WG_T == 64, "row / column assignment assumes 64-row tiles and 32-column chunks");
+  constexpr int RPT = WG_T * WG_K / 256;           // rows per thread per chunk
+  __shared__ float Gs[WG_T][WG_LD];
+  __shared__ float Xs[WG_T][WG_LD];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int m0 = blockIdx.x * WG_T, n0 = blockIdx.y * WG_T, split = blockIdx.z;
+  const long P = a.P;
+  const long nchunks = (P + WG_K - 1) / WG_K;
+  const long c_lo = (nchunks * split) / a.nsplit, c_hi = (nchunks * (split + 1)) / a.nsplit;
+  const int kk = tid & 31, rbase = tid >> 5;
+  float gv[RPT], xv[RPT];
+  auto load = [&](long c) {
+    const long k = c * WG_K + kk;
+    const bool in = k < P;
+#pragma unroll
+    for (int j = 0; j < RPT; ++j) {
+      const int m = m0 + rbase + 8 * j, n = n0 + rbase + 8 * j;
+      gv[j] = (in && m < a.M) ? a.G[(long)m * P + k] : 0.f;
+      xv[j] = (in && n < a.N) ? a.X[(long)n * P + k] : 0.f;
+    }
+  };
+  f32x16 acc;
+#pragma unroll
+  for (int q = 0; q < 16; ++q) acc[q] = 0.f;
+  const int wm = (wid & 1) * 32, wn = (wid >> 1) * 32;
+  const int l = lane & 31, h = lane >> 5;
+  if (c_lo < c_hi) load(c_lo);
+  for (long c = c_lo; c < c_hi; ++c) {
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < RPT; ++j) {
+      Gs[rbase + 8 * j][kk] = gv[j];
+      Xs[rbase + 8 * j][kk] = xv[j];
+    }
+    __syncthreads();
+    if (c + 1 < c_hi) load(c + 1);          // in flight under this chunk's MFMAs
+#pragma unroll
+    for (int st = 0; st < WG_K / 2; ++st)
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(Gs[wm + l][2 * st + h], Xs[wn + l][2 * st + h], acc, 0, 0, 0);
+  }
+  float* out = a.slab + (long)split * a.M * a.N;
+#pragma unroll
+  for (int q = 0; q < 16; ++q) {
+    const int m = m0 + wm + (q & 3) + 8 * (q >> 2) + 4 * h;
+    const int n = n0 + wn + l;
+    if (m < a.M && n < a.N) out[(long)m * a.N + n] = acc[q];
+  }
+}
+
 // Small-M variant (M <= 16: the last 3x3 layer, whose cout is the image channel count, and its dsigma):
 // VALU, one output column n per thread with all M accumulators in registers; the split runs over
 // (image, row) ranges and the pixel loop is uniform, so G[m][pixel] are scalar loads and the tap bounds
@@ -405,7 +462,7 @@ __global__ void slab_reduce_kernel(const float* slab, int nsplit, long n, float*
 // Profile tags of the weight-gradient forms: the tiled kernels record 800 + 10 TMW + TNW (811, 812, 821, 822); 899 stays
 // with the row-resident form at W = 32, the one the CIFAR-10 training step spends its VALU weight-gradient time in.
 constexpr int WGRAD_TAG_PLAIN = 890, WGRAD_TAG_VALU = 895, WGRAD_TAG_VALU3 = 896, WGRAD_TAG_VALU3R_8 = 897,
-              WGRAD_TAG_VALU3R_16 = 898, WGRAD_TAG_VALU3R_32 = 899;
+              WGRAD_TAG_VALU3R_16 = 898, WGRAD_TAG_VALU3R_32 = 899, WGRAD_TAG_FC = 891;
 
 int launch_wgrad(const WgradArgs& a0, hipStream_t s) {
   WgradArgs a = a0;
@@ -444,6 +501,30 @@ int launch_wgrad(const WgradArgs& a0, hipStream_t s) {
     if (prof) {
       const double K = (double)a.B * a.P;
       prof_end_launch(s, tag, 2.0 * a.M * a.N * K, 4.0 * K * (a.M + (double)a.N / (a.ks * a.ks)));
+    }
+    const long n = (long)a.M * a.N;
+    hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a.slab, nsplit, n,
+                       a.out);
+    INF_CHECK_LAUNCH();
+    return INF_OK;
+  }
+  if (a.fc && a.B == 1 && a.ks == 1 && !a.x_beta && a.P > 0) {
+    // the fc layout's contraction (layer_wgrad's data term; M <= 16 calls that take the VALU forms never get here):
+    // as many splits as the slab holds and the columns give, at least one chunk each
+    const int mt = (a.M + WG_T - 1) / WG_T, nt = (a.N + WG_T - 1) / WG_T;
+    const long nchunks = ((long)a.P + WG_K - 1) / WG_K;
+    int nsplit = (int)std::max<long>(1, std::min<long>(nchunks, 1024 / std::max(1, mt * nt)));
+    if (nsplit > a.max_split) nsplit = a.max_split;
+    if (nsplit < 1) nsplit = 1;
+    a.nsplit = nsplit;
+    const bool prof = prof_enabled();
+    if (prof) prof_begin_launch(s);
+    hipLaunchKernelGGL(wgrad_fc_kernel, dim3(mt, nt, nsplit), dim3(256), 0, s, a);
+    INF_CHECK_LAUNCH();
+    if (prof) {
+      const double K = (double)a.P;
+      prof_end_launch(s, WGRAD_TAG_FC, 2.0 * a.M * a.N * K, 4.0 * K * ((double)a.M + a.N),
+                      2.0 * a.M * a.N * K / PEAK_F32_FLOPS_PER_MS);
     }
     const long n = (long)a.M * a.N;
     hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a.slab, nsplit, n,

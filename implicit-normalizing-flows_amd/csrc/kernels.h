@@ -159,6 +159,10 @@ enum { LOGDET_SERIES = 0, LOGDET_EXACT = 1, LOGDET_TRACE = 2 };
 int launch_logdet_pairs(int mode, const float* tang, const float* eps, const float* x, const float* gout,
                         const float* coeff_host, int n_terms, int d, int batch, float* A, float* bv, float* xr,
                         float* value, float* a_scr, hipStream_t s);
+// the series' pairs of an fc net of any width from its two chains a (n, d, B), bs (n + 1, d, B) (series_pairs_wide_kernel)
+int launch_series_pairs_wide(const float* a, const float* bs, const float* x, const float* gout,
+                             const float* coeff_host, int n_terms, int d, int batch, float* A, float* bv, float* xr,
+                             float* value, hipStream_t s);
 int launch_sum_pairs(const float* gs, int T, int d, int batch, float* gx, hipStream_t s);
 // sample_sums: one block per sample, partial[b] = the sample's total (conv_out's OutArgs::sample_sums); stop_ev: the
 // launch completes it (hipExtLaunchKernel, not while profiling), *stop_bound set
@@ -399,6 +403,7 @@ struct WgradArgs {
   float* slab;            // nsplit * M * N floats
   float* out;             // M * N
   int nsplit, max_split;
+  int fc;                 // the data term of an fc layer (B = 1, ks = 1, no x_beta): G (M, P), X (N, P) plain matrices
 };
 int launch_wgrad(const WgradArgs& a, hipStream_t s);
 // activation algebra of the gradient chains (act: ACT_SWISH with beta, or ACT_SIN)

@@ -1740,6 +1740,67 @@ int launch_logdet_pairs(int mode, const float* tang, const float* eps, const flo
   INF_CHECK_LAUNCH();
   return INF_OK;
 }
+// The series' pairs of an fc net of any width, from the two chains instead of from J (engine_grad.hip series_pairs_chains):
+// a (n, d, B) holds a_j = (J^T)^j eps, bs (n + 1, d, B) holds b_m = J^m eps.  The first blocks write element
+// e = i N + m B + b of the three (d, N = n B) arrays, one per thread: A = g_b sum_{j<=n-1-m} c_{j+m+1} a_j, bv = b_m,
+// xr = x.  The blocks after them (value given) write value[b] = sum_k c_k eps . b_k: 64 samples per block, the d
+// features over 4 slices, summed in double in slice order.
+constexpr int SPW_SAMPLES = 64, SPW_SLICES = 4;
+__global__ __launch_bounds__(256) void series_pairs_wide_kernel(const float* a, const float* bs, const float* x,
+                                                                const float* gout, CoeffTable ct, int n_terms, int d,
+                                                                int batch, unsigned pair_blocks, float* A, float* bv,
+                                                                float* xr, float* value) {
+  const size_t N = (size_t)n_terms * batch, dB = (size_t)d * batch;
+  if (blockIdx.x < pair_blocks) {
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (size_t)d * N) return;
+    const size_t i = e / N, col = e - i * N;
+    const int m = (int)(col / batch), b = (int)(col - (size_t)m * batch);
+    const size_t ib = i * batch + b;
+    float acc = 0.f;
+    for (int j = 0; j + m < n_terms; ++j) acc = fmaf(ct.c[j + m], a[(size_t)j * dB + ib], acc);
+    A[e] = (gout ? gout[b] : 1.f) * acc;
+    bv[e] = bs[(size_t)m * dB + ib];
+    xr[e] = x[ib];
+    return;
+  }
+  __shared__ double part[SPW_SLICES][SPW_SAMPLES];
+  const int lane = threadIdx.x % SPW_SAMPLES, slice = threadIdx.x / SPW_SAMPLES;
+  const long b = (long)(blockIdx.x - pair_blocks) * SPW_SAMPLES + lane;
+  double acc = 0.0;
+  if (b < batch) {
+    const int per = (d + SPW_SLICES - 1) / SPW_SLICES;
+    const int i0 = slice * per, i1 = min(d, i0 + per);
+    for (int i = i0; i < i1; ++i) {
+      const size_t ib = (size_t)i * batch + b;
+      const float e = bs[ib];                                    // b_0 = eps
+      float t = 0.f;
+      for (int k = 1; k <= n_terms; ++k) t = fmaf(ct.c[k - 1], bs[(size_t)k * dB + ib], t);
+      acc += (double)e * t;
+    }
+  }
+  part[slice][lane] = acc;
+  __syncthreads();
+  if (slice == 0 && b < batch) {
+    double sum = 0.0;
+    for (int q = 0; q < SPW_SLICES; ++q) sum += part[q][lane];
+    value[b] = (float)sum;
+  }
+}
+int launch_series_pairs_wide(const float* a, const float* bs, const float* x, const float* gout,
+                             const float* coeff_host, int n_terms, int d, int batch, float* A, float* bv, float* xr,
+                             float* value, hipStream_t s) {
+  if (n_terms > 128 || n_terms < 1 || d < 1 || batch < 1) return INF_ERR_UNSUPPORTED;
+  CoeffTable ct;
+  for (int k = 0; k < 128; ++k) ct.c[k] = k < n_terms ? coeff_host[k] : 0.f;
+  const size_t ne = (size_t)d * n_terms * batch;
+  const size_t pb = (ne + 255) / 256, vb = value ? (size_t)(batch + SPW_SAMPLES - 1) / SPW_SAMPLES : 0;
+  if (pb + vb > 0x7fffffffUL) return INF_ERR_INVALID;
+  // reads the n a_j per element (n (n + 1) / 2 in all per (i, b)), b_m and x; writes A, bv, xr
+  INF_PROF_LAUNCH(s, 722, 4.0 * ne * (0.5 * (n_terms + 1) + 5.0), series_pairs_wide_kernel, dim3((unsigned)(pb + vb)),
+                  dim3(256), 0, s, a, bs, x, gout, ct, n_terms, d, batch, (unsigned)pb, A, bv, xr, value);
+  return INF_OK;
+}
 // gx (B, d) boundary layout = sum over the T pairs of the stacked (d, T B) x-gradient
 __global__ void sum_pairs_kernel(const float* gs, int T, int d, int batch, float* gx) {
   const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;

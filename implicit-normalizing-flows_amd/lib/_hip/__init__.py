@@ -497,13 +497,13 @@ PHASE_TAGS = {
     708: 'broyden_start_sample_kernel', 709: 'resid_bcast_sample_kernel',
     710: 'broyden_p1', 711: 'broyden_p2', 712: 'broyden_p3', 713: 'broyden_p4', 714: 'br_sum_chunks',
     715: 'broyden_small_d_kernel', 716: 'broyden_fused_kernel',
-    720: 'series_combine_kernel', 721: 'rademacher_kernel',
+    720: 'series_combine_kernel', 721: 'rademacher_kernel', 722: 'series_pairs_wide_kernel',
 }
 
 
 # The weight-gradient forms other than the tiled kernels (grad.hip launch_wgrad; the tiled ones are 8<TMW><TNW>)
 WGRAD_TAGS = {
-    890: 'wgrad_kernel', 895: 'wgrad_valu_kernel', 896: 'wgrad_valu3_kernel', 897: 'wgrad_valu3r_kernel<8>',
+    890: 'wgrad_kernel', 891: 'wgrad_fc_kernel', 895: 'wgrad_valu_kernel', 896: 'wgrad_valu3_kernel', 897: 'wgrad_valu3r_kernel<8>',
     898: 'wgrad_valu3r_kernel<16>', 899: 'wgrad_valu3r_kernel<32>',
 }
 

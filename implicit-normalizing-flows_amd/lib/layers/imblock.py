@@ -39,6 +39,10 @@ __all__ = ['imBlock', 'set_probe_mode', 'set_probe_shard', 'set_convergence', 'R
 _PROBES = {'mode': 'reference', 'seed': 0, 'offset': 0, 'shard': None}
 _SOLVE = {'convergence': 'global'}
 _MFMA_F16X3 = 2           # include/inflow.h InfMfmaMode
+_JAC_MAX = 16             # widest fc net the engine forms a per-sample Jacobian for (exact log-det, exact trace)
+# Whether fc nets wider than _JAC_MAX take their training gradients (recompute graph, series / Neumann log-det) from the
+# engine; off: the solves run on the engine and the gradients come from autograd on the module ops
+WIDE_FC_GRADS = True
 
 
 def set_probe_mode(mode, seed=0):
@@ -539,7 +543,9 @@ class imBlock(nn.Module):
                 Jz = solvers.batch_jacobian(zg + self.nnet_z(zg), zg)
                 return (torch.logdet(Jx) - torch.logdet(Jz)).view(-1, 1)
         n_ps, coeff_fn, ns = self._series_plan()
-        if self.exact_trace and engine:  # the exact-trace series and its gradients on the engine (coeff[0]: bare trace)
+        # the exact-trace series and its gradients on the engine (coeff[0]: bare trace); it needs the per-sample Jacobian,
+        # so wider nets keep the autograd branch below
+        if self.exact_trace and engine and x.shape[1] <= _JAC_MAX:
             co = np.array([1.] + [(-1) ** (k + 1) / k * coeff_fn(k) for k in range(2, n_ps + 1)], dtype=np.float32)
             nx, nz, stream = self._native(x)
             lx = _LogdetFc.apply(x, nx, self.nnet_x, netgrad.LOGDET_TRACE, None, co, False,
@@ -593,9 +599,10 @@ class imBlock(nn.Module):
 
     def _engine_grads(self, t):
         """Whether the engine computes the parameter gradients of both nets: conv nets with Swish or Sin activations
-        (a leading one included, preact), fc nets (d <= 16) with Swish / Sin; otherwise the training graph keeps
-        autograd on the nets.  (The fc nets' Neumann estimator keeps autograd for its surrogate.)"""
-        if t.dim() not in (2, 4) or (t.dim() == 2 and t.shape[1] > 16):
+        (a leading one included, preact), fc nets of any width with Swish / Sin (above d = 16 under WIDE_FC_GRADS);
+        otherwise the training graph keeps autograd on the nets.  The type rule below leaves FCNet-wrapped branches
+        (fc_end, fc=True blocks of image flows) on autograd."""
+        if t.dim() not in (2, 4) or (t.dim() == 2 and t.shape[1] > _JAC_MAX and not WIDE_FC_GRADS):
             return False
         key = '_engine_grads_ok' if t.dim() == 4 else '_engine_grads_ok_fc'
         if key not in self.__dict__:

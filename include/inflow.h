@@ -411,7 +411,10 @@ int inf_debug_readback_check(int iters, int n, void* stream);
  *   INF_LOGDET_SERIES  S_b = sum_k coeff[k-1] eps_b^T J^k eps_b, k = 1..n_terms (coeff[k-1] = (-1)^(k+1)/k coeff_fn(k));
  *   INF_LOGDET_EXACT   S_b = log|det(I + J(x_b))| (eps, coeff, n_terms unused);
  *   INF_LOGDET_TRACE   S_b = sum_k coeff[k-1] tr(J^k) (coeff[0] = 1: the bare trace).
- * x, eps (B, d) boundary layout; coeff a host array.  fc nets with Swish / Sin, d <= 16.
+ * x, eps (B, d) boundary layout; coeff a host array.  fc nets with Swish / Sin.  INF_LOGDET_SERIES takes any width: up
+ * to d = 16 its bilinear pairs come from the explicit per-sample Jacobian, above it from a VJP chain and a forward-tangent
+ * chain over the per-layer GEMMs (no Jacobian is formed).  INF_LOGDET_EXACT and INF_LOGDET_TRACE need the Jacobian: they
+ * return INF_ERR_UNSUPPORTED above d = 16 and launch nothing.  n_terms 1..128.
  * ws >= inf_logdet_grad_workspace_bytes(net, batch, mode, n_terms). */
 typedef enum InfLogdetMode { INF_LOGDET_SERIES = 0, INF_LOGDET_EXACT = 1, INF_LOGDET_TRACE = 2 } InfLogdetMode;
 size_t inf_logdet_grad_workspace_bytes(InfNet* net, int batch, int mode, int n_terms);
