@@ -147,6 +147,15 @@ int inf_rademacher(float* out, size_t n, uint64_t seed, uint64_t offset, void* s
   return glue_rademacher(out, n, seed, offset, (hipStream_t)stream);
 }
 
+int inf_net313_kernel_family(int hidden, int channels, int height, int width, int batch, int nnets, int layout_nets,
+                             int k128_policy, int mode, int f16x3) {
+  if (hidden <= 0 || channels <= 0 || height <= 0 || width <= 0 || k128_policy < 0 || k128_policy > 3 ||
+      mode < MODE_EVAL || mode > MODE_EVALSAVE)
+    return -INF_ERR_INVALID;
+  const int fam = net313_family(hidden, channels, height, width, batch, nnets, layout_nets, k128_policy, mode, f16x3 != 0);
+  return fam < 0 ? -INF_ERR_UNSUPPORTED : fam;
+}
+
 // ---- debug entries ----------------------------------------------------------------------------
 int inf_debug_poison_lds(void* stream) { return glue_poison_lds((hipStream_t)stream); }
 

@@ -17,6 +17,13 @@ using namespace inf;
 
 namespace {
 
+// The kernel family of a series term's VJP launch over `nnets` nets (a: the first, whose policy the launch follows;
+// b: the last), as launch_net313_multi decides it
+int series_family(const InfNet* a, const InfNet* b, int B, int nnets) {
+  const bool h3 = a->mfma_mode == INF_MFMA_F16X3 && b->mfma_mode == INF_MFMA_F16X3;
+  return net313_family(a->fhid, a->C, a->H, a->W, B, nnets, nnets, a->k128, MODE_VJP, h3);
+}
+
 // Power series of 1 or 2 fused nets of the same shape (the x- and z-branch of an imBlock advance in
 // lockstep: one launch per term over both nets' tiles).  Term k's VJP stages term k-1's packed taps
 // directly (tap sum, preact swish', trace partial -- conv_out's work), so a term is ONE launch; only
@@ -419,7 +426,14 @@ int inf_imblock_eval(InfNet* nx, InfNet* nz, const float* x, float* z, const flo
   // root solve (sync-bound, and short of work at the 8x8 scale) and then the z-branch series; the two streams join
   // before returning.  Concurrent series launches also desynchronise the CUs' d1/d2 bursts (every 1-WG/CU tile
   // of one launch reads its derivatives in the same phase): 2268 -> 2432 samples/s at B=64 with the 128-pixel VJP.
-  const bool overlap = nx->eval_overlap && ws_bytes >= half + zneed + xneed;
+  // The series terms run on the 128-pixel VJP kernel only where a launch's grid covers every CU (net313_family), and
+  // single-net launches that each hold a whole CU per workgroup alternate rather than share the GPU.  So where the
+  // pair launch reaches that kernel and a single-net launch would be demoted to the 64-pixel one, the block takes the
+  // sequential pair schedule: one pair launch per term beats two demoted launches, by more than the overlap hides
+  // of the root solve.
+  const bool demoted = series_family(nx, nz, B, 2) == FAM_K128 &&
+                       (series_family(nx, nx, B, 1) != FAM_K128 || series_family(nz, nz, B, 1) != FAM_K128);
+  const bool overlap = nx->eval_overlap && !demoted && ws_bytes >= half + zneed + xneed;
   if (overlap) {
     carve(nx, B, 1, w0 + half + zneed, xneed, bfc);
     bfc.D = bfa.D;                              // the x_embed pass saves f_x's derivatives into bfa.D

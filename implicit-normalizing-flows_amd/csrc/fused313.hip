@@ -1019,6 +1019,7 @@ __global__ __launch_bounds__(512) void net313_kernel_w(Net313Pair pr) {
   net313_body<TM, MODE, 32, LDS_FULL, SPL, 8, ACTK>(pr);
 }
 enum { V64 = 0, VHALF = 1, VWIDE = 2 };
+static_assert(V64 == FAM_64 && VHALF == FAM_HALF && VWIDE == FAM_WIDE, "net313_family returns the tile variant as is");
 
 static int tile_fits(int hid, int C, int H, int W, int bn, int ldsf) {
   if (!halo_tiles(H, W, bn)) return 0;
@@ -1131,6 +1132,35 @@ static void timing_collect(const char* key, long nwg, hipStream_t s) {
 // kernel times did not move (k128 VJP 15.74 vs 15.76 ms per step, s2 VJP 3.21 vs 3.16), so each XCD's L2 already serves
 // both nets' weight planes
 
+// The kernel family of a launch: a pure function of the shape, the grid and the net's policy, shared by the launcher
+// below and by callers that choose a schedule by it (engine_logdet.hip inf_imblock_eval).
+int net313_family(int hid, int C, int H, int W, int B, int nnets, int layout_nets, int k128_pol, int mode, bool h3) {
+  if (layout_nets <= 0) layout_nets = nnets;
+  if (!net313_supported(hid, C, H, W) || nnets < 1 || nnets > 2 || B < 1) return -1;
+  const int P = H * W;
+  // 64-pixel tiles unless the grid would leave CUs idle; then 32-pixel tiles two per CU; the wide
+  // variant when neither fits
+  const bool f64 = variant_fits(hid, C, H, W, V64), fh = variant_fits(hid, C, H, W, VHALF);
+  int var = f64 ? V64 : (fh ? VHALF : VWIDE);
+  // (grids counted in tiles: P / 64 and P / 32 on an exact shape, more on a ragged one.  A shape only the 64-pixel
+  // variant tiles, 32 < W < 64, keeps it however small the grid: fh is false there)
+  const int t64 = tile_count(H, W, 64), t32 = tile_count(H, W, 32);
+  if (var == V64 && (long)layout_nets * B * t64 < 256 && fh) var = VHALF;
+  // at most one 32-pixel workgroup per CU anyway: the full-LDS variant (256 VGPRs, deeper operand
+  // prefetch, paired phase-C jobs) beats the two-per-CU one (8x8 scale at B=64: 96 vs 102 us per term)
+  if (var == VHALF && (long)layout_nets * B * t32 <= 256 && variant_fits(hid, C, H, W, VWIDE)) var = VWIDE;
+  // the two-per-CU 64-pixel VJP (fused313p.hip): INF_OPT_FUSED_K128 = 3, VJP launches
+  if (mode == MODE_VJP && k128_pol == 3 && h3 && var == V64 && net313p_fits(hid, C, H, W)) return FAM_P64;
+  // 128-pixel K-chunked VJP (fused313k.hip): h3 (all phases), where the pair's derivatives are in the 64-pixel
+  // layout and the grid still covers every CU
+  // VJP / EVAL variant policy (per net, INF_OPT_FUSED_K128): 0 the 64-pixel kernel only, 1 the 128-pixel
+  // K-chunked kernel where its grid still covers every CU (default), 2 wherever it fits (tests)
+  if (k128_pol && h3 && var == V64 && net313k_fits(hid, C, H, W) &&
+      (k128_pol == 2 || (long)nnets * B * (P / 128) >= 256))
+    return FAM_K128;
+  return var;   // FAM_64 / FAM_HALF / FAM_WIDE
+}
+
 int launch_net313_multi(const Net313Args* args, int nnets, int hid, int mode, hipStream_t s, int layout_nets) {
   if (layout_nets <= 0) layout_nets = nnets;
   const Net313Args& a0 = args[0];
@@ -1139,32 +1169,15 @@ int launch_net313_multi(const Net313Args* args, int nnets, int hid, int mode, hi
   // (engine.hip fused_pair keeps such pairs off this launch)
   if ((args[0].act != 0) != (args[nnets - 1].act != 0)) return INF_ERR_INVALID;
   const int P = a0.H * a0.W;
-  // 64-pixel tiles unless the grid would leave CUs idle; then 32-pixel tiles two per CU; the wide
-  // variant when neither fits
-  const bool f64 = variant_fits(hid, a0.C, a0.H, a0.W, V64), fh = variant_fits(hid, a0.C, a0.H, a0.W, VHALF);
-  int var = f64 ? V64 : (fh ? VHALF : VWIDE);
-  // (grids counted in tiles: P / 64 and P / 32 on an exact shape, more on a ragged one.  A shape only the 64-pixel
-  // variant tiles, 32 < W < 64, keeps it however small the grid: fh is false there)
-  const int t64 = tile_count(a0.H, a0.W, 64), t32 = tile_count(a0.H, a0.W, 32);
-  if (var == V64 && layout_nets * a0.B * t64 < 256 && fh) var = VHALF;
-  // at most one 32-pixel workgroup per CU anyway: the full-LDS variant (256 VGPRs, deeper operand
-  // prefetch, paired phase-C jobs) beats the two-per-CU one (8x8 scale at B=64: 96 vs 102 us per term)
-  if (var == VHALF && layout_nets * a0.B * t32 <= 256 && variant_fits(hid, a0.C, a0.H, a0.W, VWIDE)) var = VWIDE;
-  const int bn = var == V64 ? 64 : 32;
   Net313Pair pr;
   pr.a[0] = args[0];
   pr.a[1] = args[nnets - 1];
   const bool h3_args = pr.a[0].A1h != nullptr && pr.a[1].A1h != nullptr && pr.a[0].A1s != nullptr && pr.a[1].A1s != nullptr;
-  // 128-pixel K-chunked VJP (fused313k.hip): h3 (all phases), where the pair's derivatives are in the 64-pixel
-  // layout and the grid still covers every CU
-  // VJP / EVAL variant policy (per net, INF_OPT_FUSED_K128): 0 the 64-pixel kernel only, 1 the 128-pixel
-  // K-chunked kernel where its grid still covers every CU (default), 2 wherever it fits (tests)
-  const int k128_pol = a0.k128;
-  const bool k128 = k128_pol && h3_args && var == V64 && net313k_fits(hid, a0.C, a0.H, a0.W) &&
-                    (k128_pol == 2 || (long)nnets * a0.B * (P / 128) >= 256);
-  // the two-per-CU 64-pixel VJP (fused313p.hip): INF_OPT_FUSED_K128 = 3, VJP launches
-  const bool p64 = mode == MODE_VJP && k128_pol == 3 && h3_args && var == V64 &&
-                   net313p_fits(hid, a0.C, a0.H, a0.W);
+  const int fam = net313_family(hid, a0.C, a0.H, a0.W, a0.B, nnets, layout_nets, a0.k128, mode, h3_args);
+  if (fam < 0) return INF_ERR_UNSUPPORTED;
+  const bool p64 = fam == FAM_P64, k128 = fam == FAM_K128;
+  const int var = (p64 || k128) ? V64 : fam;
+  const int bn = var == V64 ? 64 : 32;
   const int tbn = p64 ? 64 : (k128 ? 128 : bn);
   for (int i = 0; i < 2; ++i) {
     pr.a[i].seg = tile_seg(a0.W, tbn);

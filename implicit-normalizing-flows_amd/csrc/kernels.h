@@ -272,6 +272,11 @@ int launch_net313k(const Net313Pair& pr, int mode, unsigned nb, hipStream_t s);
 int net313p_fits(int hid, int C, int H, int W);
 int launch_net313p(const Net313Pair& pr, unsigned nb, hipStream_t s);
 int launch_net313(const Net313Args& a, int hid, int mode, hipStream_t s);
+// The kernel a launch of `nnets` nets (1 or 2) of this shape runs on: the 64-pixel kernel, its 32-pixel two-per-CU and
+// wide variants, the 128-pixel K-chunked kernel, the two-per-CU 64-pixel VJP.  k128_pol: the net's INF_OPT_FUSED_K128;
+// h3: both nets carry the f16x3 operands (the last two families need them); layout_nets as below.  -1: no kernel.
+enum Net313Family { FAM_64 = 0, FAM_HALF = 1, FAM_WIDE = 2, FAM_K128 = 3, FAM_P64 = 4 };
+int net313_family(int hid, int C, int H, int W, int B, int nnets, int layout_nets, int k128_pol, int mode, bool h3);
 // layout_nets (> 0) picks the tile variant as if that many nets shared the grid: launches that write
 // derivatives for a paired series must use the pair's variant (the d1/d2 layout depends on it)
 int launch_net313_multi(const Net313Args* args, int nnets, int hid, int mode, hipStream_t s, int layout_nets = 0);

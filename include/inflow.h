@@ -393,6 +393,16 @@ int inf_net_param_grad(InfNet* net, const float* x, const float* gout, float* gx
 int inf_net_surrogate_grad(InfNet* net, const float* x, const float* w, const float* eps, float* value, float* gx,
                            const InfNetGrads* grads, int batch, void* ws, size_t ws_bytes, void* stream);
 
+/* The kernel a launch of the fused 3-1-3 conv net runs on, as a pure function (no device, no net): hidden width, image
+ * shape, batch, the nets sharing the grid (1 or 2), the nets whose tile layout the launch follows (0: nnets), the
+ * INF_OPT_FUSED_K128 policy, the launch mode (0 eval, 1 derivative save, 2 VJP, 3 eval + save) and whether the nets carry
+ * the f16x3 operands.  Returns 0 the 64-pixel kernel, 1 / 2 its 32-pixel two-per-CU / wide variants, 3 the 128-pixel
+ * K-chunked kernel, 4 the two-per-CU 64-pixel VJP; negative when no fused kernel takes the shape.  inf_imblock_eval picks
+ * its schedule by it: where a pair launch of the series would run on family 3 and a single-net launch would not, the
+ * block runs the sequential pair schedule whatever INF_OPT_EVAL_OVERLAP says. */
+int inf_net313_kernel_family(int hidden, int channels, int height, int width, int batch, int nnets, int layout_nets,
+                             int k128_policy, int mode, int f16x3);
+
 /* ---- test support: fill the LDS of every CU with NaN (queued on `stream`), so a kernel that reads
  * LDS it never wrote fails deterministically instead of depending on what earlier kernels left. ---- */
 int inf_debug_poison_lds(void* stream);
