@@ -422,7 +422,7 @@ size_t inf_logdet_grad_workspace_bytes(InfNet* n, int B, int mode, int n_terms) 
 // g . S(x) differentiated into every parameter of an fc net and into x, S_b one of the log-det estimators of a sample
 // (mode INF_LOGDET_SERIES / EXACT / TRACE): the estimator's bilinear pairs at x, then one forward-over-reverse pass over
 // the T B stacked pairs (surrogate_core: the GEMM chains of the generic path, N = T B columns), the x-gradient summed
-// over each sample's pairs.  d <= 16: the pairs from the Jacobian per sample (fc_jacobian, pointwise.hip
+// over each sample's pairs.  d <= 16: the pairs from the Jacobian per sample (fc_jacobian, logdet_est.hip
 // logdet_pairs_kernel).  Wider nets, the series only: from the VJP and forward-tangent chains (series_pairs_chains); the
 // exact log-det and the exact trace need the Jacobian and stay INF_ERR_UNSUPPORTED.
 int inf_logdet_grad(InfNet* n, const float* x, int mode, const float* eps, const float* coeff, int n_terms,

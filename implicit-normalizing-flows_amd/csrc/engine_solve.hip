@@ -46,7 +46,7 @@ int sums_slot(int i, int B, SumsSlot** out) {
   return INF_OK;
 }
 // The per-sample stopping decision of step k (INF_CONV_PER_SAMPLE), queued between the reduction and the
-// readback: the device state machine (pointwise.hip ps_decide_kernel) and the copy of the improved samples'
+// readback: the device state machine (broyden.hip ps_decide_kernel) and the copy of the improved samples'
 // iterate (and f) into the lowest-iterate buffers.  The readback then carries the count of samples iterating.
 struct PsStep {
   bool on = false;

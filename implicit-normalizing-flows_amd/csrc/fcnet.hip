@@ -6,11 +6,11 @@
 // all layers with the activations in LDS:
 //
 //   FWD: f(x) for CW NCB samples, followed in-kernel by fc_out's epilogues (x_embed, the Broyden residual and its
-//        per-sample |g|^2, the z recompute; pointwise.hip fc_out_kernel), optionally after the Broyden update that
+//        per-sample |g|^2, the z recompute; out_stage.hip fc_out_kernel), optionally after the Broyden update that
 //        produces its input (br_on, fcnet_common.h broyden_update_fc);
 //   JAC: forward-mode f and its d tangents (batch_jacobian, implicit_block.py:249-260,358-362) for CW samples,
 //        NCB = d + 1 column blocks [f | df/dx_1 | ... | df/dx_d], then log|det(I + J)| per sample by partial-pivot LU
-//        in registers (torch.logdet; pointwise.hip logdet_small_kernel), the tangents, and / or the primal column's
+//        in registers (torch.logdet; logdet_est.hip logdet_small_kernel), the tangents, and / or the primal column's
 //        x_embed; the input may be the z recompute or x in the boundary layout (both written out).
 //
 // Arithmetic: exact fp32 MFMA (v_mfma_f32_16x16x4_f32, or 32x32x2 for 32-column blocks), fp32 accumulation: the generic
@@ -31,6 +31,7 @@
 #include <type_traits>
 
 #include "fcnet_common.h"
+#include "pointwise_ops.h"
 
 namespace inf {
 
@@ -240,7 +241,7 @@ __global__ __launch_bounds__(64 * NW) void fcnet_kernel(FcArgs a) {
   const float* bias = a.L[a.nl - 1].b;
 
   if constexpr (!JAC) {
-    // fc_out's epilogues (pointwise.hip fc_out_kernel), one thread per sample
+    // fc_out's epilogues (out_stage.hip fc_out_kernel; the values are pointwise_ops.h's), one thread per sample
     if (tid < S && b0 + tid < B) {
       const OutArgs& o2 = a.o;
       const long b = b0 + tid;
@@ -255,19 +256,19 @@ __global__ __launch_bounds__(64 * NW) void fcnet_kernel(FcArgs a) {
           case OM_EMBED: {
             const float v = sv + bias[c];
             o2.out0[ei] = v;
-            o2.out1[ei] = v + e0[c];
+            o2.out1[ei] = embed_value(v, e0[c]);
             break;
           }
           case OM_RESID: {
             const float v = sv + bias[c];
-            const float gx = (e0[c] - v) - e1[c];
+            const float gx = resid_value(e0[c], v, e1[c]);
             o2.out0[ei] = gx;
             if (o2.in2) o2.out1[ei] = gx - e2[c];
             if (o2.out2) o2.out2[ei] = v;
             accd += (double)gx * (double)gx;
             break;
           }
-          default: o2.out0[ei] = (e0[c] - (sv + bias[c])) + e1[c]; break;   // OM_RECOMP
+          default: o2.out0[ei] = recomp_value(e0[c], sv + bias[c], e1[c]); break;   // OM_RECOMP
         }
       }
       if (o2.partial) o2.partial[b] = accd;

@@ -8,7 +8,7 @@ namespace inf {
 constexpr int FC_H = 128;      // hidden width of the fused nets
 constexpr int FC_DMAX = 16;
 
-// The Broyden update of sample b (pointwise.hip broyden_small_kernel / broyden_small_d_kernel: the same sums in the
+// The Broyden update of sample b (broyden.hip broyden_small_kernel / broyden_small_d_kernel: the same sums in the
 // same order and precision) for the fused update + residual launch: x_new also goes to the net's input column
 // (in[k * ld], k < d), and to xn (the residual's zsub) with gx (its gprev) for the epilogue.  DD: d at compile time
 // (0: runtime d <= FC_DMAX), so that the per-column loads of several columns fit in registers and go out together.
@@ -138,7 +138,7 @@ __device__ __forceinline__ void broyden_update_fc(const BroydenArgs& a, long b, 
 }
 
 // log|det(I + J)| of one sample's DM x DM Jacobian J(i, j) by partial pivoting, in logdet_small_kernel's order of
-// operations (pointwise.hip); -inf for a singular matrix, NaN for a negative determinant (torch.logdet)
+// operations (logdet_est.hip); -inf for a singular matrix, NaN for a negative determinant (torch.logdet)
 template <int DM, typename F>
 __device__ __forceinline__ float logdet_lu(F J) {
   float M[DM][DM];

@@ -19,6 +19,7 @@
 #include <type_traits>
 
 #include "fcnet_common.h"
+#include "pointwise_ops.h"
 
 namespace inf {
 
@@ -284,7 +285,7 @@ __device__ __forceinline__ void fcnet_h3_body(const FcArgs& a, long bid) {
   const float* bias = a.L[nl - 1].b;
 
   if constexpr (!JAC) {
-    // fc_out's epilogues (pointwise.hip fc_out_kernel), one thread per sample
+    // fc_out's epilogues (out_stage.hip fc_out_kernel; the values are pointwise_ops.h's), one thread per sample
     if (tid < S && b0 + tid < B) {
       const OutArgs& o2 = a.o;
       const long b = b0 + tid;
@@ -299,19 +300,19 @@ __device__ __forceinline__ void fcnet_h3_body(const FcArgs& a, long bid) {
           case OM_EMBED: {
             const float v = sv + bias[c];
             o2.out0[ei] = v;
-            o2.out1[ei] = v + e0[c];
+            o2.out1[ei] = embed_value(v, e0[c]);
             break;
           }
           case OM_RESID: {
             const float v = sv + bias[c];
-            const float gx = (e0[c] - v) - e1[c];
+            const float gx = resid_value(e0[c], v, e1[c]);
             o2.out0[ei] = gx;
             if (o2.in2) o2.out1[ei] = gx - e2[c];
             if (o2.out2) o2.out2[ei] = v;
             accd += (double)gx * (double)gx;
             break;
           }
-          default: o2.out0[ei] = (e0[c] - (sv + bias[c])) + e1[c]; break;   // OM_RECOMP
+          default: o2.out0[ei] = recomp_value(e0[c], sv + bias[c], e1[c]); break;   // OM_RECOMP
         }
       }
       if (o2.partial) o2.partial[b] = accd;

@@ -1,7 +1,7 @@
 // Flow glue around the imBlocks (K9 of SURVEY.md §2.3) and small solver helpers.
 //   LogitTransform (elemwise.py:112-128), ActNorm (act_norm.py:153-193), squeeze (squeeze.py:242-255),
 //   standard normal log-prob (train_img.py:135-137), Rademacher probes, Banach fixed-point test
-//   (implicit_block.py:17-28), Neumann accumulation (implicit_block.py:435), forward-mode tangents.
+//   (implicit_block.py:17-28), Neumann accumulation (implicit_block.py:435), forward-mode tangents, the fc layout transpose.
 #include "kernels.h"
 #include "glue.h"
 
@@ -235,6 +235,21 @@ int glue_batched_dot(const float* a, const float* c, float* out, int B, long per
   const int nchunk = (int)((per + DOT_CHUNK - 1) / DOT_CHUNK);
   hipLaunchKernelGGL(batched_dot_partial_kernel, dim3(nchunk, B), dim3(256), 0, s, a, c, scratch, per, nchunk);
   hipLaunchKernelGGL(batched_dot_final_kernel, dim3((B + 63) / 64), dim3(64), 0, s, scratch, nchunk, B, out);
+  INF_CHECK_LAUNCH();
+  return INF_OK;
+}
+
+// boundary (B, d) <-> internal (d, B) layout of fc tensors: y[c][r] = x[r][c]
+__global__ void transpose_kernel(const float* x, float* y, int rows, int cols) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)rows * cols) return;
+  const int r = i / cols, c = i - (long)r * cols;
+  y[(long)c * rows + r] = x[i];
+}
+int launch_transpose(const float* x, float* y, int rows, int cols, hipStream_t s) {
+  const long n = (long)rows * cols;
+  if (n == 0) return INF_OK;
+  hipLaunchKernelGGL(transpose_kernel, dim3((n + 255) / 256), dim3(256), 0, s, x, y, rows, cols);
   INF_CHECK_LAUNCH();
   return INF_OK;
 }

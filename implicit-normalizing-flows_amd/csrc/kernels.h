@@ -48,7 +48,7 @@ int gemm_skinny_slices(int M, int N, int Ktot, int Kpad, size_t slab_bytes, int*
 int launch_gemm_skinny(const GemmArgs& g, int epi, float* slab, size_t slab_bytes, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------
-// Output stage of a conv net whose last layer produced packed taps Y[b][c*9+t][p] (ks = 3) or
+// Output stage (out_stage.hip).  A conv net's last layer produced packed taps Y[b][c*9+t][p] (ks = 3) or
 // plain rows Y[b][c][p] (ks = 1): s = sum_t Y[..][shift_t(p)], then a fused epilogue.
 // ------------------------------------------------------------------------------------------
 enum OutMode { OM_PLAIN = 0, OM_EMBED = 1, OM_RESID = 2, OM_RECOMP = 3, OM_VJP = 4 };
@@ -80,29 +80,45 @@ int launch_conv_out(const OutArgs& a, int batch, hipStream_t s);
 
 // fc nets: feature-major (d, B) tensors.  Up to FC_NARROW_MAX features: one thread per sample for the per-sample
 // reductions, one partial per sample (nchunk = 1).  Wider nets: a grid over (feature chunk, sample block) with
-// out_nchunk(d) partials per sample, as conv_out (pointwise.hip fc_out_wide_kernel); so do launch_resid_bcast_fc and
+// out_nchunk(d) partials per sample, as conv_out (out_stage.hip fc_out_wide_kernel); so do launch_resid_bcast_fc and
 // launch_vjp_resid.
 constexpr int FC_NARROW_MAX = 32;
 inline int fc_nchunk(int d) { return d > FC_NARROW_MAX ? out_nchunk(d) : 1; }
 int launch_fc_out(const OutArgs& a, int batch, hipStream_t s);
+// stop_ev (optional, here and below): an event the launch itself completes (hipExtLaunchKernel; not while profiling);
+// *stop_bound, where given, is then set
+int launch_reduce_partials(const double* partial, int batch, int nchunk, double* out, hipStream_t s,
+                           hipEvent_t stop_ev = nullptr, bool* stop_bound = nullptr);
+// The first residual of a root solve from the cached f(0) (f0: one sample's values).  Conv layout; sample_sums: one
+// block per sample, partial[b] = the sample's total (conv_out's OutArgs::sample_sums)
+int launch_resid_bcast(const float* f0, const float* xemb, const float* z, float* g, float* fcur, double* partial,
+                       int batch, int per, int nchunk, hipStream_t s, int sample_sums = 0, hipEvent_t stop_ev = nullptr,
+                       bool* stop_bound = nullptr);
+// conv layout, per-sample sums (d <= 4 OUT_CH chunks): x0 = 0, the residual at it, update = -g0, x1 = x0 + update,
+// dx = x1 - x0 in one launch, one block per sample, partial[b] the sample's sum of squares
+int launch_broyden_start_sample(const float* f0, const float* xemb, float* x0, float* g, float* fcur, double* partial,
+                                hipEvent_t stop_ev, bool* stop_bound, float* upd, float* x1, float* dx, int batch,
+                                int per, hipStream_t s);
+// fc layout (d, B): f0 holds d values
+int launch_resid_bcast_fc(const float* f0, const float* xemb, const float* z, float* g, float* fcur, double* partial,
+                          int batch, int d, hipStream_t s);
+// x0 = 0, the residual at it, update = -g0, x1 = x0 + update, dx = x1 - x0 in one launch (fc layout)
+int launch_broyden_start_fc(const float* f0, const float* xemb, float* x0, float* g, float* fcur, double* partial,
+                            hipEvent_t stop_ev, bool* stop_bound, float* upd, float* x1, float* dx, int batch, int d, hipStream_t s);
+// the implicit backward's residual g = (y + v) - grad, dg = g - gprev (gprev nullable), partial sums of g^2
+int launch_vjp_resid(const float* v, const float* y, const float* grad, const float* gprev, float* g, float* dg,
+                     double* partial, int batch, int d, int nchunk, int fc, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------
-// misc elementwise / layout
+// Broyden (broyden.hip): the step kernels, the low-rank algebra (broyden.py:101-120,174-181), per-sample,
+// layout-generic, and the per-sample rule's state machine.
+//   element i of sample b lives at b * sb + i * si;  U/VT column j of sample b at
+//   j * cs + b * sb + i * si  (cs = column stride).
 // ------------------------------------------------------------------------------------------
-int launch_transpose(const float* x, float* y, int rows, int cols, hipStream_t s);  // y[c][r] = x[r][c]
 int launch_axpy_step(const float* x, const float* upd, float* xnew, float* dx, long n, hipStream_t s);
 int launch_neg(const float* x, float* y, long n, hipStream_t s);
 // x_est = x0 + sc * upd, dx = x_est - x0 (the line search's trial point; product and sum rounded separately)
 int launch_line_step(const float* x, const float* upd, float sc, float* xnew, float* dx, long n, hipStream_t s);
-// stop_ev (optional): an event the launch itself completes (hipExtLaunchKernel; not while profiling), *stop_bound set
-int launch_reduce_partials(const double* partial, int batch, int nchunk, double* out, hipStream_t s,
-                           hipEvent_t stop_ev = nullptr, bool* stop_bound = nullptr);
-
-// ------------------------------------------------------------------------------------------
-// Broyden low-rank algebra (broyden.py:101-120,174-181), per-sample, layout-generic:
-//   element i of sample b lives at b * sb + i * si;  U/VT column j of sample b at
-//   j * cs + b * sb + i * si  (cs = column stride).
-// ------------------------------------------------------------------------------------------
 struct BroydenArgs {
   int batch, d, T;
   long sb, si, cs;
@@ -122,7 +138,7 @@ struct BroydenArgs {
 };
 int launch_broyden_update(const BroydenArgs& a, hipStream_t s);
 
-// per-sample convergence (INF_CONV_PER_SAMPLE, pointwise.hip): the stopping rules of broyden.py:153-172 per sample
+// per-sample convergence (INF_CONV_PER_SAMPLE): the stopping rules of broyden.py:153-172 per sample
 constexpr int PS_HEAD = 8;   // doubles of per-sample state before the objective ring
 // ss: B per-sample sums of squares (+1: receives the number of samples still iterating); k = step (0: initial)
 int launch_ps_decide(double* ss, double* state, int* active, int* improved, int B, int k, int T, double eps,
@@ -132,6 +148,9 @@ int launch_ps_copy(const int* improved, const float* x, const float* f, float* l
 int launch_ps_fixed_point(const float* x, const float* xp, const float* y, float* result, int* todo, int B, int d,
                           long sb, long si, float eps, int force, hipStream_t s);
 
+// ------------------------------------------------------------------------------------------
+// Operand preparation (prep.hip)
+// ------------------------------------------------------------------------------------------
 // Spectral scale: sigma = u . (W v) for conv (pad k//2) or matrix; factor = max(1, sigma / coeff)
 constexpr int SIGMA_MAX_PARTS = 4096;   // launch_sigma's partial count bound when it splits channels
 int launch_sigma(const float* W, const float* u, const float* v, int cout, int cin, int ks, int H, int Wd,
@@ -145,16 +164,27 @@ int launch_pack(const float* W, const float* factor, float* dst, int cout, int c
 // Split a fragment-major fp32 operand (n = Mpad * Kpad floats) into three bf16 planes per 512-float
 // fragment tile: dst[(tile * 3 + plane) * 512 + w] (fused313.hip split phase B).
 int launch_split3(const float* src, uint16_t* dst, long n, hipStream_t s);
-// Scale exponent of a whole operand (*exp_out = h3_scale_exp(max |src|), common.h) and its two scaled fp16
-// planes per 512-float fragment tile: dst[(tile * 2 + plane) * 512 + w] (fused313.hip phase B, F16X3).
+// *exp_out = h3_scale_exp(max |src|) (common.h)
+int launch_amax_exp(const float* src, long n, int* exp_out, hipStream_t s);
+// Scale exponent of a whole operand (launch_amax_exp) and its two scaled fp16 planes per 512-float fragment tile:
+// dst[(tile * 2 + plane) * 512 + w] (fused313.hip phase B, F16X3).
 int launch_split2h(const float* src, uint16_t* dst, long n, int* exp_out, hipStream_t s);
 // Copy of fragment-major fp16 planes (launch_split2h layout, ntiles fragment tiles of 2 x 512 halves) with the k index
 // of every 32x16 fragment tile permuted: slot (lane (i, h), 4a + q) <- slot (lane (i, a), 4h + q), i.e. k bits 2, 3 swapped
 int launch_permute_k23(const uint16_t* src, uint16_t* dst, long ntiles, hipStream_t s);
 
+// ------------------------------------------------------------------------------------------
+// Log-det estimators of fc nets and the series combine (logdet_est.hip)
+// ------------------------------------------------------------------------------------------
+// forward-mode activation on [primal | ntang tangent blocks] (d_out, (1 + ntang) B): a -> act(a), t -> act'(a) t
+int launch_fwdmode_act(float* a, float* deriv, int d_out, int batch, int ntang, int act, const float* beta,
+                       hipStream_t s);
 // exact small log-det per sample: J[b] = I + T[b] with T stored tangents (d, d, B) feature-major
 int launch_logdet_small(const float* tang, float* out, int d, int batch, long stride_j, hipStream_t s);
-// the log-det estimators' gradients as stacked (A, b) pairs at x (pointwise.hip logdet_pairs_kernel; fc nets, d <= 16)
+// exact-trace power series sum_k c_k tr(J^k) per sample (d <= 16)
+int launch_trace_series(const float* tang, const float* coeff, int n_terms, float* out, int d, int batch,
+                        long stride_j, hipStream_t s);
+// the log-det estimators' gradients as stacked (A, b) pairs at x (logdet_pairs_kernel; fc nets, d <= 16)
 enum { LOGDET_SERIES = 0, LOGDET_EXACT = 1, LOGDET_TRACE = 2 };
 int launch_logdet_pairs(int mode, const float* tang, const float* eps, const float* x, const float* gout,
                         const float* coeff_host, int n_terms, int d, int batch, float* A, float* bv, float* xr,
@@ -164,31 +194,12 @@ int launch_series_pairs_wide(const float* a, const float* bs, const float* x, co
                              const float* coeff_host, int n_terms, int d, int batch, float* A, float* bv, float* xr,
                              float* value, hipStream_t s);
 int launch_sum_pairs(const float* gs, int T, int d, int batch, float* gx, hipStream_t s);
-// sample_sums: one block per sample, partial[b] = the sample's total (conv_out's OutArgs::sample_sums); stop_ev: the
-// launch completes it (hipExtLaunchKernel, not while profiling), *stop_bound set
-int launch_resid_bcast(const float* f0, const float* xemb, const float* z, float* g, float* fcur, double* partial,
-                       int batch, int per, int nchunk, hipStream_t s, int sample_sums = 0, hipEvent_t stop_ev = nullptr,
-                       bool* stop_bound = nullptr);
-// conv layout, per-sample sums (d <= 4 OUT_CH chunks): x0 = 0, the residual at it, update = -g0, x1 = x0 + update,
-// dx = x1 - x0 in one launch, one block per sample, partial[b] the sample's sum of squares
-int launch_broyden_start_sample(const float* f0, const float* xemb, float* x0, float* g, float* fcur, double* partial,
-                                hipEvent_t stop_ev, bool* stop_bound, float* upd, float* x1, float* dx, int batch,
-                                int per, hipStream_t s);
-// fc layout (d, B): f0 holds d values
-int launch_resid_bcast_fc(const float* f0, const float* xemb, const float* z, float* g, float* fcur, double* partial,
-                          int batch, int d, hipStream_t s);
-// x0 = 0, the residual at it, update = -g0, x1 = x0 + update, dx = x1 - x0 in one launch (fc layout)
-int launch_broyden_start_fc(const float* f0, const float* xemb, float* x0, float* g, float* fcur, double* partial,
-                            hipEvent_t stop_ev, bool* stop_bound, float* upd, float* x1, float* dx, int batch, int d, hipStream_t s);
-int launch_vjp_resid(const float* v, const float* y, const float* grad, const float* gprev, float* g, float* dg,
-                     double* partial, int batch, int d, int nchunk, int fc, hipStream_t s);
-int launch_trace_series(const float* tang, const float* coeff, int n_terms, float* out, int d, int batch,
-                        long stride_j, hipStream_t s);
-int launch_fwdmode_act(float* a, float* deriv, int d_out, int batch, int ntang, int act, const float* beta,
-                       hipStream_t s);
-
+// out[b] = sum_k fl(c_k * tr_k[b]), tr_k the chunk-ordered sum of the term's partials (coeff: host, n_terms <= 128)
 int launch_series_combine(const double* partials, const float* coeff_dev, int n_terms, int batch, int nchunk,
                           float* out, hipStream_t s);
+
+// layout helper (glue.hip): y[c][r] = x[r][c]
+int launch_transpose(const float* x, float* y, int rows, int cols, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------
 // fused 3-1-3 conv net (fused313.hip): one launch per forward / derivative-saving forward / VJP
@@ -340,8 +351,6 @@ int launch_fcnet_h3_jac_pair(const FcArgs& a0, const FcArgs& a1, hipStream_t s);
 // fc weight planes for the f16x3 kernels: the packed (M rows used, Kpad) fp32 operand -> nrt x nks fragment tiles of
 // 16 rows x 32 k, two scaled fp16 planes each, *exp_out = h3_scale_exp(max |A|)
 int launch_fc_split_h3(const float* A, int M, int Kpad, int nrt, int nks, uint16_t* dst, int* exp_out, hipStream_t s);
-// *exp_out = h3_scale_exp(max |src|) (pointwise.hip)
-int launch_amax_exp(const float* src, long n, int* exp_out, hipStream_t s);
 
 // one launch per fused fc imBlock evaluation (fcblock.hip): x-branch log-det and x_embed, the Broyden root solve with its
 // state in LDS (global rule: one tagged fp64 partial per workgroup and iteration; per-sample rule: no exchange), the z

@@ -490,7 +490,7 @@ def profile_end():
                  bytes=arr[i].bytes, peak_ms=arr[i].peak_ms) for i in range(min(n.value, 256))]
 
 
-# Profiled launches of the HBM-bound phases (pointwise.hip / glue.hip INF_PROF_LAUNCH): tag -> kernel name (the
+# Profiled launches of the HBM-bound phases (out_stage.hip / broyden.hip / logdet_est.hip / glue.hip INF_PROF_LAUNCH): tag -> kernel name (the
 # rocprofv3 Kernel_Name without namespace, template arguments and signature)
 PHASE_TAGS = {
     700: 'resid_bcast_kernel', 701: 'resid_bcast_fc_kernel', 702: 'broyden_start_fc_kernel', 703: 'axpy_step_kernel',
@@ -510,7 +510,7 @@ WGRAD_TAGS = {
 
 
 def tag_name(tag):
-    """Human/rocprof-readable name of a kernel tag (see gemm.hip run<> / pointwise.hip)."""
+    """Human/rocprof-readable name of a kernel tag (see gemm.hip run<> / out_stage.hip)."""
     if tag in PHASE_TAGS:
         return PHASE_TAGS[tag]
     if 500 <= tag < 540:     # 50x: net313_kernel (64-px tiles), 51x: _h (32-px, 2 per CU), 52x: _w (32-px, wide),
@@ -529,7 +529,7 @@ def tag_name(tag):
         return WGRAD_TAGS[tag]
     if 960 <= tag <= 962:    # per-layer GEMMs of fc nets wider than 32 features (gemm_skinny.hip)
         return ['gemm_skinny_kernel<split-K partial>', 'gemm_skinny_reduce_kernel', 'gemm_skinny_kernel<small tile>'][tag - 960]
-    if 950 <= tag <= 955:    # output stage of fc nets wider than 32 features (pointwise.hip), 95<mode>
+    if 950 <= tag <= 955:    # output stage of fc nets wider than 32 features (out_stage.hip), 95<mode>
         return 'fc_out_wide_kernel<%s>' % ['PLAIN', 'EMBED', 'RESID', 'RECOMP', 'VJP', 'VJPRES'][tag - 950]
     if 800 <= tag < 900:     # tiled weight-gradient kernel (grad.hip), 8<TMW><TNW>
         return 'wgrad_tiled_kernel<%d,%d>' % ((tag - 800) // 10, tag % 10)

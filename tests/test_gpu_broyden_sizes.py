@@ -1,4 +1,4 @@
-"""The limited-memory Broyden update (pointwise.hip launch_broyden_update, through inf_broyden_update) at every size
+"""The limited-memory Broyden update (broyden.hip launch_broyden_update, through inf_broyden_update) at every size
 its launcher dispatches on, against broyden.py:174-181 restated in fp64 (oracle _rmatvec / _matvec on the fp32 inputs):
 
   * small      d <= 32:            broyden_small_d_kernel<2 | 6 | 8> or the generic broyden_small_kernel      tag 715
@@ -21,7 +21,7 @@ from oracle.inflow_oracle import _matvec, _rmatvec
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
-CH = 1024                      # pointwise.hip BR_CH
+CH = 1024                      # broyden.hip BR_CH
 
 
 def _regime(d):

@@ -261,7 +261,7 @@ def test_protective_break_banach_fallback_matches_reference(golden_dir, converge
 @pytest.mark.parametrize('d', [2, 6, 7, 8])
 @pytest.mark.parametrize('nstep', [1, 3, 5])
 def test_broyden_update_small_d_matches_reference_algebra(d, nstep):
-    """The per-sample Broyden update of the small-d kernels (pointwise.hip: broyden_small_d_kernel<2 / 6 / 8>, the
+    """The per-sample Broyden update of the small-d kernels (broyden.hip: broyden_small_d_kernel<2 / 6 / 8>, the
     generic broyden_small_kernel for d = 7) through inf_broyden_update, against broyden.py:174-181 restated in fp64
     (oracle _rmatvec / _matvec).  The columns no step has written yet (j >= nstep) hold NaN: the update must not read
     them (broyden_core no longer zeroes U / VT per solve), so the result equals the zero-filled run bit for bit."""

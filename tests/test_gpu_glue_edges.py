@@ -1,5 +1,5 @@
 """The small solver and glue kernels through the C ABI at the sizes where they take another branch, against fp64 torch
-on the CPU: the line-search trial point (pointwise.hip line_step_kernel), ActNorm (glue.hip actnorm_kernel: the float4
+on the CPU: the line-search trial point (broyden.hip line_step_kernel), ActNorm (glue.hip actnorm_kernel: the float4
 path, the scalar path for hw % 4 != 0 or pointers off a 16-byte boundary, the channel loop for C > 256), the logit
 transform, the standard-normal log-prob, squeeze and the Rademacher generator.
 

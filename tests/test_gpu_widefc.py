@@ -1,6 +1,6 @@
 """Fully connected nets with more than 32 input features on the engine.
 
-Such nets run the generic GEMM chain with the wide output stage (pointwise.hip fc_out_wide_kernel: a grid over feature
+Such nets run the generic GEMM chain with the wide output stage (out_stage.hip fc_out_wide_kernel: a grid over feature
 chunks of 1024 and sample blocks, per-chunk fp64 partials), and their Broyden state stays feature-major (d, B): the
 update kernels for d > 32 (broyden_fused_kernel, broyden_p1..p4, br_sum_chunks) reach it through their strides.
 
@@ -30,7 +30,7 @@ from oracle import inflow_oracle as orc
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
-CH = 1024                       # pointwise.hip OUT_CH / BR_CH
+CH = 1024                       # out_stage.hip OUT_CH / broyden.hip BR_CH
 
 
 def _arch(d, act='sin', **kw):
