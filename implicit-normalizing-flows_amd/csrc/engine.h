@@ -95,6 +95,7 @@ struct InfNet {
   int fc_block = 1;        // INF_OPT_FC_BLOCK (read on net_z of inf_imblock_eval_exact)
   int fc_series = 1;       // INF_OPT_FC_SERIES (read on the first net of inf_logdet_series[_pair])
   int fc_skinny = 1;       // INF_OPT_FC_SKINNY (fc nets over more than FC_NARROW_MAX features: layer_gemm)
+  int series_group = 0;    // INF_OPT_SERIES_GROUP (read on the first net of a fused series: 0 the rule, else samples per group)
   // fused fc path (fcnet.hip): the whole net in one launch per evaluation (forward and forward-mode Jacobian)
   bool fcfused = false;
   // f16x3 planes of the fused fc layers (fcnet_h3.hip, filled at refresh): layer l at fch + fch_off[l], exponent fchexp[l]

@@ -156,6 +156,16 @@ int inf_net313_kernel_family(int hidden, int channels, int height, int width, in
   return fam < 0 ? -INF_ERR_UNSUPPORTED : fam;
 }
 
+int inf_series_group(int hidden, int channels, int height, int width, int batch, int nnets, int concurrent,
+                     int k128_policy, int f16x3) {
+  if (hidden <= 0 || channels <= 0 || height <= 0 || width <= 0 || batch <= 0 || nnets < 1 || nnets > 2 ||
+      concurrent < 1 || k128_policy < 0 || k128_policy > 3)
+    return -INF_ERR_INVALID;
+  if (net313_family(hidden, channels, height, width, batch, nnets, nnets, k128_policy, MODE_VJP, f16x3 != 0) < 0)
+    return -INF_ERR_UNSUPPORTED;
+  return net313_series_group(hidden, channels, height, width, batch, nnets, concurrent, k128_policy, f16x3 != 0);
+}
+
 // ---- debug entries ----------------------------------------------------------------------------
 int inf_debug_poison_lds(void* stream) { return glue_poison_lds((hipStream_t)stream); }
 

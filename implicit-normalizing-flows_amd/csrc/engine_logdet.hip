@@ -17,11 +17,14 @@ using namespace inf;
 
 namespace {
 
+// whether both nets of a series launch carry the f16x3 operands
+bool series_h3(const InfNet* a, const InfNet* b) {
+  return a->mfma_mode == INF_MFMA_F16X3 && b->mfma_mode == INF_MFMA_F16X3;
+}
 // The kernel family of a series term's VJP launch over `nnets` nets (a: the first, whose policy the launch follows;
 // b: the last), as launch_net313_multi decides it
 int series_family(const InfNet* a, const InfNet* b, int B, int nnets) {
-  const bool h3 = a->mfma_mode == INF_MFMA_F16X3 && b->mfma_mode == INF_MFMA_F16X3;
-  return net313_family(a->fhid, a->C, a->H, a->W, B, nnets, nnets, a->k128, MODE_VJP, h3);
+  return net313_family(a->fhid, a->C, a->H, a->W, B, nnets, nnets, a->k128, MODE_VJP, series_h3(a, b));
 }
 
 // Power series of 1 or 2 fused nets of the same shape (the x- and z-branch of an imBlock advance in
@@ -32,50 +35,78 @@ int series_family(const InfNet* a, const InfNet* b, int B, int nnets) {
 // Neumann mode (wouts != nullptr, ncoeff a host array of n_terms + 1): instead of the trace partials, each
 // term's staging accumulates w += ncoeff[k] v_k for its own pixels (w starts as eps, the last term's taps go
 // through conv_out), i.e. the Neumann vector of implicit_block.py:430-436 for 1 or 2 nets in lockstep.
+//
+// Sample groups (INF_OPT_SERIES_GROUP): the series is independent per sample (the 3x3 halo never crosses
+// an image), so it runs as one complete chain per group of G samples, a group's derivative-saving forward directly in
+// front of its terms: the d1 / d2 planes live between two terms, read again by every term, are then a group's and not
+// the whole batch's (the rule sizes a group to the memory-side cache).  A group's buffers are the batch's own, sliced
+// by pointer: every per-sample buffer moves by the group's first sample (the pair layout included: each net's planes are its own buffer, indexed by the net's own
+// tiles), the trace slab's base too while its term stride stays B x snchunk.  Each group launches on the whole batch's
+// kernel family and its tiles do the whole batch's arithmetic: bitwise the same results for every G.  The closing
+// conv_out / combine launches stay one over the whole batch.  concurrent: the series running side by side with this one
+// included (inf_imblock_eval's overlapped schedule: 2).
 int series_fused(InfNet* const* nets, const float* const* xs, const float* const* es, int nn, const float* coeff,
                  int n_terms, float* const* outs, int B, Bufs* bfs, hipStream_t s, unsigned save_mask = 3u,
-                 float* const* wouts = nullptr, const float* ncoeff = nullptr) {
-  Net313Args args[2];
+                 float* const* wouts = nullptr, const float* ncoeff = nullptr, int concurrent = 1) {
+  const InfNet* n0 = nets[0];
+  const int fam = series_family(n0, nets[nn - 1], B, nn);
+  if (fam < 0) return INF_ERR_UNSUPPORTED;
   for (int i = 0; i < nn; ++i) {
-    args[i] = net313_args(nets[i], xs[i], B, bfs[i], false);
     if (!wouts) INF_HIP(hipMemsetAsync(bfs[i].part, 0, sizeof(double) * n_terms * B * bfs[i].snchunk, s));
     else INF_HIP(hipMemcpyAsync(wouts[i], es[i], sizeof(float) * (size_t)B * nets[i]->d, hipMemcpyDeviceToDevice, s));
   }
-  // activation derivatives (in the pair's tile layout); a net whose d1/d2 are already saved is skipped
+  const int G = n0->series_group > 0 ? std::min(n0->series_group, B)
+                                     : net313_series_group(n0->fhid, n0->C, n0->H, n0->W, B, nn, concurrent, n0->k128,
+                                                           series_h3(n0, nets[nn - 1]));
+  // per-sample strides of the sliced buffers: d1 / d2 in the family's tile layout, the packed taps, the vectors
+  const size_t dstr = net313_dstride(n0->fhid, n0->H, n0->W, fam), ystr = (size_t)n0->M3 * n0->P, vstr = (size_t)n0->d;
   const unsigned all = (1u << nn) - 1u;
-  if ((save_mask & all) == all) {
-    INF_TRY(launch_net313_multi(args, nn, nets[0]->fhid, MODE_SAVE, s));
-  } else {
-    for (int i = 0; i < nn; ++i)
-      if (save_mask & (1u << i)) INF_TRY(launch_net313_multi(&args[i], 1, nets[0]->fhid, MODE_SAVE, s, nn));
-  }
-  for (int k = 0; k < n_terms; ++k) {
-    for (int i = 0; i < nn; ++i) {
-      InfNet* n = nets[i];
-      Bufs& bf = bfs[i];
-      Net313Args& v = args[i];
-      v = net313_args(n, es[i], B, bf, true);
-      v.Y = (k % 2 == 0) ? bf.Y : bf.Y2;
-      // serpentine: odd terms walk the tiles backwards, so a term starts on the derivative tiles the previous
-      // one read last (still in the memory-side cache: s0 pair 349 -> 338 us per term)
-      v.tile_order = k & 1;
-      if (k > 0) {
-        v.in = nullptr;
-        v.in_taps = (k % 2 == 1) ? bf.Y : bf.Y2;
-        v.vmul_x = n->pre_act != ACT_NONE ? xs[i] : nullptr;
-        v.vmul_beta = n->pre_beta;
-        v.vmul_act = n->pre_act == ACT_SWISH ? 0 : n->pre_act;
-        if (wouts) {
-          v.acc_w = wouts[i];
-          v.acc_coef = ncoeff[k];
-        } else {
-          v.dot_eps = es[i];
-          v.dot_part = bf.part + (size_t)(k - 1) * B * bf.snchunk;
-          v.dot_nchunk = bf.snchunk;
+  Net313Args args[2];
+  for (int g0 = 0; g0 < B; g0 += G) {
+    const int Bg = std::min(G, B - g0);
+    auto group_args = [&](int i, const float* in, bool vjp) {
+      Net313Args v = net313_args(nets[i], in + g0 * vstr, Bg, bfs[i], vjp);
+      v.d1 += g0 * dstr;
+      v.d2 += g0 * dstr;
+      v.Y += g0 * ystr;
+      return v;
+    };
+    // activation derivatives (in the pair's tile layout); a net whose d1/d2 are already saved is skipped
+    for (int i = 0; i < nn; ++i) args[i] = group_args(i, xs[i], false);
+    if ((save_mask & all) == all) {
+      INF_TRY(launch_net313_multi(args, nn, n0->fhid, MODE_SAVE, s, 0, B));
+    } else {
+      for (int i = 0; i < nn; ++i)
+        if (save_mask & (1u << i)) INF_TRY(launch_net313_multi(&args[i], 1, n0->fhid, MODE_SAVE, s, nn, B));
+    }
+    for (int k = 0; k < n_terms; ++k) {
+      for (int i = 0; i < nn; ++i) {
+        InfNet* n = nets[i];
+        Bufs& bf = bfs[i];
+        Net313Args& v = args[i];
+        v = group_args(i, es[i], true);
+        v.Y = ((k % 2 == 0) ? bf.Y : bf.Y2) + g0 * ystr;
+        // serpentine: odd terms walk the tiles backwards, so a term starts on the derivative tiles the previous
+        // one read last (still in the memory-side cache: s0 pair 349 -> 338 us per term)
+        v.tile_order = k & 1;
+        if (k > 0) {
+          v.in = nullptr;
+          v.in_taps = ((k % 2 == 1) ? bf.Y : bf.Y2) + g0 * ystr;
+          v.vmul_x = n->pre_act != ACT_NONE ? xs[i] + g0 * vstr : nullptr;
+          v.vmul_beta = n->pre_beta;
+          v.vmul_act = n->pre_act == ACT_SWISH ? 0 : n->pre_act;
+          if (wouts) {
+            v.acc_w = wouts[i] + g0 * vstr;
+            v.acc_coef = ncoeff[k];
+          } else {
+            v.dot_eps = es[i] + g0 * vstr;
+            v.dot_part = bf.part + ((size_t)(k - 1) * B + g0) * bf.snchunk;
+            v.dot_nchunk = bf.snchunk;
+          }
         }
       }
+      INF_TRY(launch_net313_multi(args, nn, n0->fhid, MODE_VJP, s, 0, B));
     }
-    INF_TRY(launch_net313_multi(args, nn, nets[0]->fhid, MODE_VJP, s));
   }
   // the last term's taps through conv_out: its trace partial, or (Neumann) its vector added to w
   for (int i = 0; i < nn; ++i) {
@@ -459,7 +490,8 @@ int inf_imblock_eval(InfNet* nx, InfNet* nz, const float* x, float* z, const flo
     INF_HIP(hipStreamWaitEvent(side->s, side->fork, 0));
     join.side = side;
     join.s = s;
-    INF_TRY(series_fused(&nx, &x, &eps_x, 1, coeff, n_terms, &logdet_x, B, &bfc, side->s, /*save_mask=*/0u));
+    INF_TRY(series_fused(&nx, &x, &eps_x, 1, coeff, n_terms, &logdet_x, B, &bfc, side->s, /*save_mask=*/0u, nullptr, nullptr,
+                         /*concurrent=*/2));
   }
   InfBroydenStats st = stats_for(stats);
   INF_TRY(broyden_solve(nz, x, B, T, eps, &st, nullptr, bfa, s));
@@ -476,7 +508,8 @@ int inf_imblock_eval(InfNet* nx, InfNet* nz, const float* x, float* z, const flo
   }
   if (overlap) {
     const float* zin = z;
-    return series_fused(&nz, &zin, &eps_z, 1, coeff, n_terms, &logdet_z, B, &bfb, s, /*save_mask=*/1u);   // join: ~SideJoin
+    return series_fused(&nz, &zin, &eps_z, 1, coeff, n_terms, &logdet_z, B, &bfb, s, /*save_mask=*/1u, nullptr, nullptr,
+                        /*concurrent=*/2);   // join: ~SideJoin
   }
   InfNet* nets[2] = {nx, nz};
   const float* xs[2] = {x, z};

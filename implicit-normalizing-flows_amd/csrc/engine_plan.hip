@@ -82,6 +82,7 @@ const NetOption OPTIONS[] = {
     {INF_OPT_FC_SERIES, &InfNet::fc_series, 1, "INFLOW_FC_SERIES", {"0", "1"}, false},
     {INF_OPT_FC_SKINNY, &InfNet::fc_skinny, 1, nullptr, {}, false},
     {INF_OPT_FUSED_PRESPLIT, &InfNet::presplit, 1, "INFLOW_FUSED_PRESPLIT", {"0", "1"}, false},
+    {INF_OPT_SERIES_GROUP, &InfNet::series_group, INF_SERIES_GROUP_OFF, nullptr, {}, false},
 };
 const NetOption* find_option(int id) {
   for (const NetOption& o : OPTIONS)

@@ -1161,7 +1161,30 @@ int net313_family(int hid, int C, int H, int W, int B, int nnets, int layout_net
   return var;   // FAM_64 / FAM_HALF / FAM_WIDE
 }
 
-int launch_net313_multi(const Net313Args* args, int nnets, int hid, int mode, hipStream_t s, int layout_nets) {
+// Floats per sample of a net's d1 (or d2) plane as a launch of family `fam` indexes it: hidden x tiles x tile width, in
+// the 64-pixel layout for the 128-pixel and two-per-CU kernels too (H * W * hid on an exact shape)
+size_t net313_dstride(int hid, int H, int W, int fam) {
+  const int bn = (fam == FAM_HALF || fam == FAM_WIDE) ? 32 : 64;
+  return (size_t)hid * tile_count(H, W, bn) * bn;
+}
+
+// Samples per group of a power series run as one complete chain per group of samples (engine_logdet.hip series_fused):
+// the largest group whose derivative planes, over the `concurrent` series in flight and the `nnets` nets of a launch,
+// stay within SERIES_PLANE_BUDGET, and whose launches (the short last group's included) run on the kernel family of the
+// full-batch launch.  B: no grouping (the planes fit as they are, or no admissible group exists).
+int net313_series_group(int hid, int C, int H, int W, int B, int nnets, int concurrent, int k128_pol, bool h3) {
+  const int fam = net313_family(hid, C, H, W, B, nnets, nnets, k128_pol, MODE_VJP, h3);
+  if (fam < 0 || concurrent < 1) return B;
+  const size_t per_sample = (size_t)concurrent * nnets * net313_dstride(hid, H, W, fam) * sizeof(float) * 2;
+  if (per_sample * B <= SERIES_PLANE_BUDGET) return B;
+  auto keeps = [&](int g) { return net313_family(hid, C, H, W, g, nnets, nnets, k128_pol, MODE_VJP, h3) == fam; };
+  for (int g = (int)std::min<size_t>(B - 1, SERIES_PLANE_BUDGET / per_sample); g >= 1; --g)
+    if (keeps(g) && (B % g == 0 || keeps(B % g))) return g;
+  return B;
+}
+
+int launch_net313_multi(const Net313Args* args, int nnets, int hid, int mode, hipStream_t s, int layout_nets,
+                        int family_batch) {
   if (layout_nets <= 0) layout_nets = nnets;
   const Net313Args& a0 = args[0];
   if (!net313_supported(hid, a0.C, a0.H, a0.W) || nnets < 1 || nnets > 2) return INF_ERR_UNSUPPORTED;
@@ -1173,7 +1196,9 @@ int launch_net313_multi(const Net313Args* args, int nnets, int hid, int mode, hi
   pr.a[0] = args[0];
   pr.a[1] = args[nnets - 1];
   const bool h3_args = pr.a[0].A1h != nullptr && pr.a[1].A1h != nullptr && pr.a[0].A1s != nullptr && pr.a[1].A1s != nullptr;
-  const int fam = net313_family(hid, a0.C, a0.H, a0.W, a0.B, nnets, layout_nets, a0.k128, mode, h3_args);
+  // (a sample group of a series launches on the kernel family of the whole batch: family_batch)
+  const int fam = net313_family(hid, a0.C, a0.H, a0.W, family_batch > 0 ? family_batch : a0.B, nnets, layout_nets, a0.k128,
+                                mode, h3_args);
   if (fam < 0) return INF_ERR_UNSUPPORTED;
   const bool p64 = fam == FAM_P64, k128 = fam == FAM_K128;
   const int var = (p64 || k128) ? V64 : fam;

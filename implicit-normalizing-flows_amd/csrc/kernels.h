@@ -290,7 +290,19 @@ enum Net313Family { FAM_64 = 0, FAM_HALF = 1, FAM_WIDE = 2, FAM_K128 = 3, FAM_P6
 int net313_family(int hid, int C, int H, int W, int B, int nnets, int layout_nets, int k128_pol, int mode, bool h3);
 // layout_nets (> 0) picks the tile variant as if that many nets shared the grid: launches that write
 // derivatives for a paired series must use the pair's variant (the d1/d2 layout depends on it)
-int launch_net313_multi(const Net313Args* args, int nnets, int hid, int mode, hipStream_t s, int layout_nets = 0);
+// family_batch (> 0) picks the kernel family as if the launch held that many samples: a sample group of a series runs
+// on the family, and so the d1 / d2 layout, of the whole batch
+int launch_net313_multi(const Net313Args* args, int nnets, int hid, int mode, hipStream_t s, int layout_nets = 0,
+                        int family_batch = 0);
+// Floats per sample of d1 (or d2) in the layout a launch of family `fam` reads and writes
+size_t net313_dstride(int hid, int H, int W, int fam);
+// The bytes of activation-derivative planes (d1 + d2 of every net of every series in flight) a series keeps live between
+// two terms before it is run in sample groups: the size of the memory-side cache.  Settled by timings (DESIGN.md §3e:
+// groups of 32 at the 32x32 scale gain, groups of 16 lose it again); FETCH_SIZE does not show what the cache serves
+constexpr size_t SERIES_PLANE_BUDGET = (size_t)256 << 20;
+// Samples per group of a series over B samples (B: one group), a pure function: `nnets` nets per launch, `concurrent`
+// series running side by side, k128_pol / h3 as for net313_family
+int net313_series_group(int hid, int C, int H, int W, int B, int nnets, int concurrent, int k128_pol, bool h3);
 
 // ------------------------------------------------------------------------------------------
 // fused fc net (fcnet.hip): the tabular / toy nets, one launch per evaluation

@@ -24,6 +24,8 @@ INF_ERR_UNSUPPORTED = 4       # InfStatus (include/inflow.h)
 INF_OPT_FUSED_K128, INF_OPT_EVAL_OVERLAP, INF_OPT_CONVERGENCE, INF_OPT_K128_EXACT_SCALE = 1, 2, 3, 4   # InfNetOption
 INF_OPT_FC_BLOCK, INF_OPT_FC_SERIES, INF_OPT_LINE_SEARCH, INF_OPT_FUSED_PRESPLIT = 5, 6, 7, 8
 INF_OPT_FC_SKINNY = 9         # wide fc nets' layers on the skinny GEMM family (gemm_skinny.hip); 0: the generic GEMM
+INF_OPT_SERIES_GROUP = 11        # samples per group of a fused conv series: 0 the rule (inf_series_group), g >= 1 forced
+INF_SERIES_GROUP_OFF = 1 << 30   # ... and this value never groups
 INF_CONV_GLOBAL, INF_CONV_PER_SAMPLE = 0, 1                                # InfConvergence
 CONVERGENCE = {'global': INF_CONV_GLOBAL, 'per_sample': INF_CONV_PER_SAMPLE}
 
@@ -145,6 +147,7 @@ _SIGS = {
     'inf_profile_end': (ctypes.c_int, [ctypes.POINTER(KernelStat), ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
     'inf_rademacher': (ctypes.c_int, [_P, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint64, _P]),
     'inf_net313_kernel_family': (ctypes.c_int, [ctypes.c_int] * 10),
+    'inf_series_group': (ctypes.c_int, [ctypes.c_int] * 9),
     'inf_debug_poison_lds': (ctypes.c_int, [_P]),
     'inf_debug_readback_check': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _P]),
     'inf_net_set_option': (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int]),

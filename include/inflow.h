@@ -184,6 +184,15 @@ int inf_net_get_mfma(const InfNet* net);
  *                         layer on the generic GEMM, as before round 13.  The workspace does not depend on the value.
  *                         Other nets ignore it.  Results agree to fp32 roundoff between the values.  It has no environment
  *                         variable: inf_net_set_option is the one way to change it.
+ *   INF_OPT_SERIES_GROUP  read on the first net of a power series of fused 3-1-3 conv nets (inf_logdet_series[_pair],
+ *                         inf_neumann_vector_pair, inf_imblock_eval): the series is independent per sample, so it may run
+ *                         as complete chains over groups of samples, one group after the other, each group's
+ *                         derivative-saving forward directly in front of its terms, so that the activation-derivative
+ *                         planes live between two terms are one group's, not the batch's.  0 (default) takes the rule
+ *                         inf_series_group; g >= 1 forces g samples per group (the last group may be short; g >= batch is
+ *                         one group), and INF_SERIES_GROUP_OFF never groups.  Every group launches on the kernel the whole
+ *                         batch would: bitwise the same results for every value.  It has no environment variable.
+ *                         (Option id 10 is unassigned.)
  * Unknown values of INFLOW_FUSED_K128 (0-3), INFLOW_FC_BLOCK (0/1/2), INFLOW_EVAL_OVERLAP / INFLOW_FC_SERIES (0/1) and INFLOW_CONVERGENCE (global/per_sample)
  * make inf_net_create fail with INF_ERR_INVALID.
  * FUSED_K128, EVAL_OVERLAP and K128_EXACT_SCALE are performance / test knobs without a reference counterpart (the reference
@@ -192,8 +201,9 @@ int inf_net_get_mfma(const InfNet* net);
 typedef enum InfNetOption {
   INF_OPT_FUSED_K128 = 1, INF_OPT_EVAL_OVERLAP = 2, INF_OPT_CONVERGENCE = 3, INF_OPT_K128_EXACT_SCALE = 4,
   INF_OPT_FC_BLOCK = 5, INF_OPT_FC_SERIES = 6, INF_OPT_LINE_SEARCH = 7, INF_OPT_FUSED_PRESPLIT = 8,
-  INF_OPT_FC_SKINNY = 9
+  INF_OPT_FC_SKINNY = 9, INF_OPT_SERIES_GROUP = 11
 } InfNetOption;
+#define INF_SERIES_GROUP_OFF (1 << 30)
 typedef enum InfConvergence { INF_CONV_GLOBAL = 0, INF_CONV_PER_SAMPLE = 1 } InfConvergence;
 int inf_net_set_option(InfNet* net, int option, int value);
 int inf_net_get_option(const InfNet* net, int option);
@@ -402,6 +412,16 @@ int inf_net_surrogate_grad(InfNet* net, const float* x, const float* w, const fl
  * block runs the sequential pair schedule whatever INF_OPT_EVAL_OVERLAP says. */
 int inf_net313_kernel_family(int hidden, int channels, int height, int width, int batch, int nnets, int layout_nets,
                              int k128_policy, int mode, int f16x3);
+
+/* Samples per group of a power series of fused 3-1-3 conv nets under INF_OPT_SERIES_GROUP = 0, as a pure function (no
+ * device, no net): the nets of one launch (1 or 2), the series running side by side (2 under inf_imblock_eval's
+ * overlapped schedule, else 1), the INF_OPT_FUSED_K128 policy and whether the nets carry the f16x3 operands.  The live
+ * planes are concurrent x nnets x group x (d1 + d2 of one sample) bytes; where the whole batch's exceed 256 MiB (the
+ * memory-side cache), the result is the largest group whose planes do not and whose launches, the short last group's
+ * included, still run on the kernel family of the whole batch's launch (inf_net313_kernel_family in VJP mode).  Returns
+ * `batch` for one group (the planes fit, or no such group exists); negative for invalid arguments or an unfused shape. */
+int inf_series_group(int hidden, int channels, int height, int width, int batch, int nnets, int concurrent,
+                     int k128_policy, int f16x3);
 
 /* ---- test support: fill the LDS of every CU with NaN (queued on `stream`), so a kernel that reads
  * LDS it never wrote fails deterministically instead of depending on what earlier kernels left. ---- */

@@ -1,6 +1,8 @@
 """Run only the paired log-det series of one CIFAR10 scale (for rocprofv3 counter passes).
 
-    python tools/series_only.py --scale 0 --batch 64 --mfma 1 --reps 3
+    python tools/series_only.py --scale 0 --batch 64 --mfma 1 --reps 3 [--group G]
+
+--group: INF_OPT_SERIES_GROUP (0 the rule, G >= 1 samples per group, -1 never grouped).
 """
 import argparse
 import ctypes
@@ -22,6 +24,7 @@ ap.add_argument('--reps', type=int, default=3)
 ap.add_argument('--terms', type=int, default=20)
 ap.add_argument('--k128', type=int, default=1, help='INF_OPT_FUSED_K128')
 ap.add_argument('--single', type=int, default=0, help='one net (inf_logdet_series) instead of the pair')
+ap.add_argument('--group', type=int, default=0, help='INF_OPT_SERIES_GROUP; -1: INF_SERIES_GROUP_OFF')
 a = ap.parse_args()
 arch = syn.CIFAR10
 B = a.batch
@@ -42,6 +45,7 @@ for n_ in (nx, nz):
     n_.refresh_if_needed(st)
     _hip.check(n_.lib.inf_net_set_mfma(n_.handle, a.mfma), 'set')
     n_.set_option(_hip.INF_OPT_FUSED_K128, a.k128)
+    n_.set_option(_hip.INF_OPT_SERIES_GROUP, _hip.INF_SERIES_GROUP_OFF if a.group < 0 else a.group)
 ws = torch.empty(2 * max(nx.ws_bytes(B), nz.ws_bytes(B)), dtype=torch.uint8, device='cuda')
 out = torch.empty(2, B, device='cuda')
 co = np.array([(-1) ** (k + 1) / k for k in range(1, a.terms + 1)], dtype=np.float32)
@@ -61,5 +65,5 @@ for r in range(a.reps + 1):
 t1.record()
 torch.cuda.synchronize()
 us = t0.elapsed_time(t1) / a.reps / a.terms * 1e3
-print('scale %d B %d mfma %d k128 %d %s: %.1f us/term, %.3f us/term/image' % (
-    a.scale, B, a.mfma, a.k128, 'single' if a.single else 'pair', us, us / B / (1 if a.single else 2)))
+print('scale %d B %d mfma %d k128 %d group %d %s: %.1f us/term, %.3f us/term/image' % (
+    a.scale, B, a.mfma, a.k128, a.group, 'single' if a.single else 'pair', us, us / B / (1 if a.single else 2)))
