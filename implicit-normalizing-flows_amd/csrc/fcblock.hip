@@ -21,433 +21,16 @@
 #include <cstring>
 #include <utility>
 
-#include "fcnet_common.h"
+#include "fcblock_pass.h"
 
 namespace inf {
 
 namespace {
-constexpr int BK_NW = 8;
-constexpr int BK_NT = 64 * BK_NW;
-constexpr int BK_LD = FC_H + 8;     // halves per activation-plane column (fcnet_h3.hip)
-constexpr int BK_S = 48;            // samples per workgroup
-constexpr int BK_FCB = BK_S / 16;   // FWD column blocks
 constexpr unsigned BK_SPIN_MAX = 1u << 22;
 constexpr int BK_NSETS = 4;       // granule sets of the global rule's exchange (gather_k)
 
-// Phase stamps (INFLOW_PHASE_STAMPS builds only, tools/build_stamps_fcblock.sh): thread 0 of every workgroup records
-// s_memtime after each barrier-delimited stage; the launch prints the per-stage means.  Null buffer otherwise.
-constexpr int BK_TSLOTS = 128;
-struct Stamps {
-  unsigned long long* buf;
-  int i;
-};
-#if INFLOW_PHASE_STAMPS
-#define BK_STAMP(T_)                                                                              \
-  do {                                                                                            \
-    if ((T_) && (T_)->buf && threadIdx.x == 0 && (T_)->i < BK_TSLOTS)                             \
-      (T_)->buf[(long)blockIdx.x * BK_TSLOTS + (T_)->i++] = __builtin_amdgcn_s_memtime();         \
-  } while (0)
-#else
-#define BK_STAMP(T_) \
-  do {               \
-    (void)(T_);      \
-  } while (0)
-#endif
-
-// Workgroup barrier for LDS traffic only: waits for this wave's LDS operations, not for its global loads (the weight
-// requests in flight across a layer's barriers; __syncthreads() would drain them: s_waitcnt vmcnt(0)).  Every
-// intra-workgroup exchange of this kernel goes through LDS.
-__device__ __forceinline__ void bk_sync() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 typedef __attribute__((address_space(1))) unsigned long long gu64;
 typedef __attribute__((address_space(1))) unsigned int gu32;
-
-__device__ __forceinline__ f32x4 mfma3(const u32x4 (&a)[2], const u32x4& xh, const u32x4& xl, f32x4 c) {
-  const f16x8 ah = __builtin_bit_cast(f16x8, a[0]), al = __builtin_bit_cast(f16x8, a[1]);
-  const f16x8 bh = __builtin_bit_cast(f16x8, xh), bl = __builtin_bit_cast(f16x8, xl);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, c, 0, 0, 0);
-  return c;
-}
-
-template <int NKS>
-__device__ __forceinline__ void ldw(const uint16_t* A, int nks, int rt, int lane, u32x4 (&w)[NKS][2]) {
-  const u32x4* p = reinterpret_cast<const u32x4*>(A);
-#pragma unroll
-  for (int ks = 0; ks < NKS; ++ks) {
-    const long t = (long)rt * nks + ks;
-    w[ks][0] = p[(t * 2 + 0) * 64 + lane];
-    w[ks][1] = p[(t * 2 + 1) * 64 + lane];
-  }
-}
-
-__device__ __forceinline__ void split4(const float (&v)[4], float S, uint2& h, uint2& l) {
-  _Float16 hh[4], ll[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    hh[r] = (_Float16)(v[r] * S);
-    ll[r] = (_Float16)__builtin_fmaf(v[r], S, -(float)hh[r]);
-  }
-  const f16x2 a = {hh[0], hh[1]}, b = {hh[2], hh[3]}, c = {ll[0], ll[1]}, e = {ll[2], ll[3]};
-  h = make_uint2(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b));
-  l = make_uint2(__builtin_bit_cast(unsigned, c), __builtin_bit_cast(unsigned, e));
-}
-
-// A net's resident weights for the solve: the hidden layers' fragments of wave w in registers; the input layer's fp32
-// rows (exact VALU contraction, fcnet_common.h fc_in_col; [row][BK_W0_LD], k >= d zero) and the output layer (four k
-// steps, row tile 0) as fragment planes in LDS (12 KiB at 128 wide)
-template <int NH>
-struct NetRegs {
-  u32x4 wh[NH][4][2];
-  const float* w0;   // LDS: [row * BK_W0_LD + k], row < 128, k < d
-  const u32x4* wo;   // LDS: [(ks * 2 + plane) * 64 + lane], ks < 4
-};
-constexpr int BK_W0_LD = 8;               // floats per input-layer row in LDS (d <= 8)
-constexpr int BK_W0_VEC = FC_H * BK_W0_LD / 4;   // u32x4 of the input layer's fp32 rows
-constexpr int BK_WO_VEC = 4 * 2 * 64;     // u32x4 of the output layer's planes
-template <int NH>
-__device__ __forceinline__ void load_net(const FcArgs& a, int w, int lane, u32x4* lds_w, NetRegs<NH>& r) {
-  const u32x4* go = reinterpret_cast<const u32x4*>(a.L[NH + 1].Ah);
-  float* w0 = reinterpret_cast<float*>(lds_w);
-  for (int i = threadIdx.x; i < FC_H * BK_W0_LD; i += BK_NT) {
-    const int row = i / BK_W0_LD, k = i - row * BK_W0_LD;
-    w0[i] = k < a.d ? a.L[0].A[(long)row * a.L[0].Kpad + k] : 0.f;
-  }
-  for (int i = threadIdx.x; i < BK_WO_VEC; i += BK_NT) lds_w[BK_W0_VEC + i] = go[i];
-#pragma unroll
-  for (int l = 0; l < NH; ++l) ldw<4>(a.L[1 + l].Ah, 4, w, lane, r.wh[l]);
-  r.w0 = w0;
-  r.wo = lds_w + BK_W0_VEC;
-}
-
-// the activation derivatives a forward pass saves for the VJP passes of the power series (mlp_pass SV modes)
-enum { SV_NONE = 0, SV_SAVE = 1, SV_VJP = 2 };
-template <int NH, int NCB>
-struct Derivs {
-  float d[NH + 1][NCB][4];
-};
-
-// LDS scratch of one pass over NC columns
-struct Pass {
-  uint16_t* pl0;   // [col][k] h plane
-  uint16_t* pl1;   // l plane
-  float* tmp;      // [row][col] fp32 input rows [0, 16) / output rows [0, 16)
-  float* wmax;     // [wave][col]
-  int* sx;         // column scale exponents
-};
-
-// One pass of the net over NC = 16 NCB columns: inputs in tmp rows [0, 16) (rows >= d zero), the output layer's sums
-// (no bias) left in tmp rows [0, 16).  The arithmetic of fcnet_h3.hip per column: the input layer (K = DD) in exact fp32
-// on the VALU from the fp32 rows, the others scaled two-piece fp16 operands, three products per fp32 product on
-// v_mfma_f32_16x16x32_f16, fp32 accumulation, exact unscale.  JAC: column block 0 is the
-// primal, the others are tangents, multiplied by act'(pre-activation of the primal).  REG: the weights come from
-// registers (loaded once per solve) instead of global memory.  SV_SAVE: a forward pass that also keeps act' of
-// every hidden unit in D (registers: wave w holds rows 16 w + 4 g + r of every hidden layer); SV_VJP: the pass of the
-// transposed net (a.L[j] = W_{L-1-j}^T, fcseries_kernel) whose hidden epilogue is the product with D's derivatives of
-// forward layer NH - j instead of bias + activation -- the row ownership of both passes is the same.
-template <int DD, int NCB, bool JAC, int ACT, int NH, bool REG, int SV = SV_NONE, class NA = FcArgs>
-__device__ __forceinline__ void mlp_pass(const NA& a, const NetRegs<NH>* R, const Pass& P, Stamps* ts,
-                                         Derivs<NH, NCB>* D = nullptr) {
-  constexpr int NC = 16 * NCB;
-  const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int li = lane & 15, g = lane >> 4;
-  u32x4 wnext[4][2];
-  u32x4 w0[1][2];                              // (unused: the input layer is the VALU contraction)
-  float wi[4][DD];
-  if constexpr (!REG) {
-    fc_in_weights<DD>(a.L[0].A, a.L[0].Kpad, DD, 16 * w + 4 * g, wi);
-    if (NH > 0) ldw<4>(a.L[1].Ah, 4, w, lane, wnext);
-  }
-  bk_sync();                                   // the caller's input rows (and, REG, the resident weights)
-  if constexpr (REG) fc_in_weights<DD>(R->w0, BK_W0_LD, DD, 16 * w + 4 * g, wi);
-  BK_STAMP(ts);
-
-  auto layer = [&](auto nksc, int l, const u32x4 (&wr)[decltype(nksc)::value][2]) {
-    constexpr int NKS = decltype(nksc)::value;
-    const FcLayer& L = a.L[l];
-    float bias[4];
-    if constexpr (SV != SV_VJP) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) bias[r] = L.b[16 * w + 4 * g + r];
-    }
-    const float sp = (ACT == ACT_SWISH && SV != SV_VJP) ? softplus_f(ldc(L.beta)) : 0.f;
-    float v[NCB][4];
-    if constexpr (NKS == 1) {
-#pragma unroll
-      for (int cb = 0; cb < NCB; ++cb) fc_in_col<DD>(wi, P.tmp + cb * 16 + li, NC, DD, v[cb]);
-    } else {
-      f32x4 acc[NCB];
-#pragma unroll
-      for (int cb = 0; cb < NCB; ++cb) acc[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < NKS; ++ks)
-#pragma unroll
-        for (int cb = 0; cb < NCB; ++cb) {
-          const int col = cb * 16 + li;
-          const u32x4 xh = *reinterpret_cast<const u32x4*>(P.pl0 + col * BK_LD + ks * 32 + 8 * g);
-          const u32x4 xl = *reinterpret_cast<const u32x4*>(P.pl1 + col * BK_LD + ks * 32 + 8 * g);
-          acc[cb] = mfma3(wr[ks], xh, xl, acc[cb]);
-        }
-      const int sw = ldc(L.Aexp);
-#pragma unroll
-      for (int cb = 0; cb < NCB; ++cb) {
-        const int e = -(sw + P.sx[cb * 16 + li]);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[cb][r] = __builtin_amdgcn_ldexpf(acc[cb][r], e);
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      if constexpr (SV == SV_VJP) {
-#pragma unroll
-        for (int cb = 0; cb < NCB; ++cb) v[cb][r] *= D->d[NH - l][cb][r];
-      } else if constexpr (SV == SV_SAVE) {
-#pragma unroll
-        for (int cb = 0; cb < NCB; ++cb) fc_act_fd<ACT>(v[cb][r] + bias[r], sp, v[cb][r], D->d[l][cb][r]);
-      } else if constexpr (JAC) {
-        const float z = v[0][r] + bias[r];
-        float dd;
-        fc_act_fd<ACT>(z, sp, v[0][r], dd);
-#pragma unroll
-        for (int cb = 1; cb < NCB; ++cb) v[cb][r] *= dd;
-      } else {
-#pragma unroll
-        for (int cb = 0; cb < NCB; ++cb) v[cb][r] = fc_act_f<ACT>(v[cb][r] + bias[r], sp);
-      }
-    }
-    // Sin nets: the fixed scales of fcnet_h3.hip (the forward and primal values in [-1/(2 pi), 1/(2 pi)], the tangents
-    // bounded by the Lipschitz caps where every coeff <= 1) -- no column-max exchange; else per-column maxima.  (The
-    // transposed passes of the series keep per-column scales: their vectors carry the probe's norm.)
-    bool allfix = false;
-    if constexpr (ACT == ACT_SIN && SV != SV_VJP) {
-      if constexpr (JAC) allfix = a.tan_fixed != 0;
-      else allfix = true;
-    }
-    if (allfix) {
-      bk_sync();                                 // every wave is done reading this layer's input planes
-#pragma unroll
-      for (int cb = 0; cb < NCB; ++cb) {
-        const int col = cb * 16 + li;
-        const int e = (JAC && cb > 0) ? FC_SFIXT : FC_SFIX;
-        uint2 h, lo;
-        split4(v[cb], __builtin_amdgcn_ldexpf(1.f, e), h, lo);
-        *reinterpret_cast<uint2*>(P.pl0 + col * BK_LD + 16 * w + 4 * g) = h;
-        *reinterpret_cast<uint2*>(P.pl1 + col * BK_LD + 16 * w + 4 * g) = lo;
-        if (w == 0 && g == 0) P.sx[col] = e;
-      }
-    } else {
-#pragma unroll
-      for (int cb = 0; cb < NCB; ++cb) {
-        float m = fmaxf(fmaxf(fabsf(v[cb][0]), fabsf(v[cb][1])), fmaxf(fabsf(v[cb][2]), fabsf(v[cb][3])));
-        m = fmaxf(m, __shfl_xor(m, 16, 64));
-        m = fmaxf(m, __shfl_xor(m, 32, 64));
-        if (g == 0) P.wmax[w * NC + cb * 16 + li] = m;
-      }
-      bk_sync();
-#pragma unroll
-      for (int cb = 0; cb < NCB; ++cb) {
-        const int col = cb * 16 + li;
-        float m = 0.f;
-#pragma unroll
-        for (int ww = 0; ww < BK_NW; ++ww) m = fmaxf(m, P.wmax[ww * NC + col]);
-        const int e = (ACT == ACT_SIN && SV != SV_VJP && cb == 0) ? FC_SFIX : h3_scale_exp(m);
-        uint2 h, lo;
-        split4(v[cb], __builtin_amdgcn_ldexpf(1.f, e), h, lo);
-        *reinterpret_cast<uint2*>(P.pl0 + col * BK_LD + 16 * w + 4 * g) = h;
-        *reinterpret_cast<uint2*>(P.pl1 + col * BK_LD + 16 * w + 4 * g) = lo;
-        if (w == 0 && g == 0) P.sx[col] = e;
-      }
-    }
-    bk_sync();
-    BK_STAMP(ts);
-  };
-  if constexpr (REG) {
-    layer(std::integral_constant<int, 1>(), 0, w0);
-#pragma unroll
-    for (int l = 0; l < NH; ++l) layer(std::integral_constant<int, 4>(), 1 + l, R->wh[l]);
-  } else {
-    layer(std::integral_constant<int, 1>(), 0, w0);
-#pragma unroll
-    for (int l = 0; l < NH; ++l) {
-      u32x4 wc[4][2];
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        wc[ks][0] = wnext[ks][0];
-        wc[ks][1] = wnext[ks][1];
-      }
-      if (l + 1 < NH) ldw<4>(a.L[2 + l].Ah, 4, w, lane, wnext);
-      layer(std::integral_constant<int, 4>(), 1 + l, wc);
-    }
-  }
-  // output layer: 16 padded rows (d valid), K = 128; column block w on wave w
-  if (w < NCB) {
-    const FcLayer& L = a.L[NH + 1];
-    u32x4 wo[4][2];
-    if constexpr (REG) {
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        wo[ks][0] = R->wo[(ks * 2 + 0) * 64 + lane];
-        wo[ks][1] = R->wo[(ks * 2 + 1) * 64 + lane];
-      }
-    } else {
-      ldw<4>(L.Ah, 4, 0, lane, wo);
-    }
-    const int col = w * 16 + li;
-    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      const u32x4 xh = *reinterpret_cast<const u32x4*>(P.pl0 + col * BK_LD + ks * 32 + 8 * g);
-      const u32x4 xl = *reinterpret_cast<const u32x4*>(P.pl1 + col * BK_LD + ks * 32 + 8 * g);
-      acc = mfma3(wo[ks], xh, xl, acc);
-    }
-    const int e = -(ldc(L.Aexp) + P.sx[col]);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) P.tmp[(4 * g + r) * NC + col] = __builtin_amdgcn_ldexpf(acc[r], e);
-  }
-  bk_sync();
-  BK_STAMP(ts);
-}
-
-// The forward-mode Jacobian pass (JAC of mlp_pass) with half the LDS operand traffic: the 8 waves form 4 row groups of
-// 32 rows (two 16-row tiles each, both fed by every B fragment read) x 2 column groups; column group c takes the primal
-// column block 0 and tangent blocks [1 + c NT / 2, 1 + (c + 1) NT / 2) (the primal is computed by both groups: each
-// needs act' of its rows).  The arithmetic per column is mlp_pass's (same products, same order, same scales); weights
-// stream from global memory, each layer's requested right after the previous layer's products.
-template <int DD, int NCB, int ACT, int NH>
-__device__ __forceinline__ void mlp_jac2(const FcArgs& a, const Pass& P, Stamps* ts) {
-  constexpr int NC = 16 * NCB;
-  constexpr int NT = NCB - 1;                 // tangent blocks (even)
-  constexpr int NJ = 1 + NT / 2;              // column blocks per wave
-  static_assert(NT % 2 == 0, "even tangent count");
-  const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int li = lane & 15, g = lane >> 4;
-  const int rg = w & 3, cg = w >> 2;
-  auto cbof = [&](int j) { return j == 0 ? 0 : j + cg * (NT / 2); };
-  u32x4 wi[2][1][2];                           // (unused: the input layer is the VALU contraction)
-  float wf[2][4][DD];
-  fc_in_weights<DD>(a.L[0].A, a.L[0].Kpad, DD, 16 * (2 * rg + 0) + 4 * g, wf[0]);
-  fc_in_weights<DD>(a.L[0].A, a.L[0].Kpad, DD, 16 * (2 * rg + 1) + 4 * g, wf[1]);
-  u32x4 wh[2][4][2];
-  if (NH > 0) {
-    ldw<4>(a.L[1].Ah, 4, 2 * rg + 0, lane, wh[0]);
-    ldw<4>(a.L[1].Ah, 4, 2 * rg + 1, lane, wh[1]);
-  }
-  bk_sync();                                   // the caller's input rows
-  BK_STAMP(ts);
-  auto layer = [&](auto nksc, int l, u32x4 (&wr)[2][decltype(nksc)::value][2]) {
-    constexpr int NKS = decltype(nksc)::value;
-    const FcLayer& L = a.L[l];
-    const float sp = (ACT == ACT_SWISH) ? softplus_f(ldc(L.beta)) : 0.f;
-    float v[2][NJ][4];
-    if constexpr (NKS == 1) {
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) fc_in_col<DD>(wf[t], P.tmp + cbof(j) * 16 + li, NC, DD, v[t][j]);
-    } else {
-      f32x4 acc[2][NJ];
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) acc[t][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < NKS; ++ks)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-          const int col = cbof(j) * 16 + li;
-          const u32x4 xh = *reinterpret_cast<const u32x4*>(P.pl0 + col * BK_LD + ks * 32 + 8 * g);
-          const u32x4 xl = *reinterpret_cast<const u32x4*>(P.pl1 + col * BK_LD + ks * 32 + 8 * g);
-          acc[0][j] = mfma3(wr[0][ks], xh, xl, acc[0][j]);
-          acc[1][j] = mfma3(wr[1][ks], xh, xl, acc[1][j]);
-        }
-      // the next hidden layer's weights, in flight during this epilogue
-      if (l + 1 <= NH) {
-        ldw<4>(a.L[l + 1].Ah, 4, 2 * rg + 0, lane, wh[0]);
-        ldw<4>(a.L[l + 1].Ah, 4, 2 * rg + 1, lane, wh[1]);
-      }
-      const int sw = ldc(L.Aexp);
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        const int e = -(sw + P.sx[cbof(j) * 16 + li]);
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[t][j][r] = __builtin_amdgcn_ldexpf(acc[t][j][r], e);
-      }
-    }
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float z = v[t][0][r] + L.b[16 * (2 * rg + t) + 4 * g + r];
-        float dd;
-        fc_act_fd<ACT>(z, sp, v[t][0][r], dd);
-#pragma unroll
-        for (int j = 1; j < NJ; ++j) v[t][j][r] *= dd;
-      }
-    const bool allfix = ACT == ACT_SIN && a.tan_fixed;   // (mlp_pass's fixed scales)
-    if (!allfix) {
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        float m = 0.f;
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-          m = fmaxf(m, fmaxf(fmaxf(fabsf(v[t][j][0]), fabsf(v[t][j][1])), fmaxf(fabsf(v[t][j][2]), fabsf(v[t][j][3]))));
-        m = fmaxf(m, __shfl_xor(m, 16, 64));
-        m = fmaxf(m, __shfl_xor(m, 32, 64));
-        if (g == 0 && (j > 0 || cg == 0)) P.wmax[rg * NC + cbof(j) * 16 + li] = m;
-      }
-    }
-    bk_sync();
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      if (j == 0 && cg != 0) continue;           // the primal's planes come from column group 0
-      const int col = cbof(j) * 16 + li;
-      int e;
-      if (allfix) {
-        e = j == 0 ? FC_SFIX : FC_SFIXT;
-      } else {
-        const float m = fmaxf(fmaxf(P.wmax[0 * NC + col], P.wmax[1 * NC + col]),
-                              fmaxf(P.wmax[2 * NC + col], P.wmax[3 * NC + col]));
-        e = (ACT == ACT_SIN && j == 0) ? FC_SFIX : h3_scale_exp(m);
-      }
-      const float S2 = __builtin_amdgcn_ldexpf(1.f, e);
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        uint2 h, lo;
-        split4(v[t][j], S2, h, lo);
-        *reinterpret_cast<uint2*>(P.pl0 + col * BK_LD + 16 * (2 * rg + t) + 4 * g) = h;
-        *reinterpret_cast<uint2*>(P.pl1 + col * BK_LD + 16 * (2 * rg + t) + 4 * g) = lo;
-      }
-      if (rg == 0 && g == 0) P.sx[col] = e;
-    }
-    bk_sync();
-    BK_STAMP(ts);
-  };
-  layer(std::integral_constant<int, 1>(), 0, wi);
-#pragma unroll
-  for (int l = 0; l < NH; ++l) layer(std::integral_constant<int, 4>(), 1 + l, wh);
-  // output layer: 16 padded rows (d valid), K = 128; column block w on wave w
-  if (w < NCB) {
-    const FcLayer& L = a.L[NH + 1];
-    u32x4 wo[4][2];
-    ldw<4>(L.Ah, 4, 0, lane, wo);
-    const int col = w * 16 + li;
-    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      const u32x4 xh = *reinterpret_cast<const u32x4*>(P.pl0 + col * BK_LD + ks * 32 + 8 * g);
-      const u32x4 xl = *reinterpret_cast<const u32x4*>(P.pl1 + col * BK_LD + ks * 32 + 8 * g);
-      acc = mfma3(wo[ks], xh, xl, acc);
-    }
-    const int e = -(ldc(L.Aexp) + P.sx[col]);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) P.tmp[(4 * g + r) * NC + col] = __builtin_amdgcn_ldexpf(acc[r], e);
-  }
-  bk_sync();
-  BK_STAMP(ts);
-}
 
 // ---- the global rule's exchange: one fp64 per workgroup and iteration as two tagged 32-bit granules -------------------
 // (the R2 form of cdna_hip_programming.md Guideline 16: the data is the flag; 8-byte relaxed agent-scope stores and
@@ -599,7 +182,6 @@ struct BkLayout {
   int S, DD, T;
   size_t vec, ps_d, ps_i, ring, ctl, uni, jac, fwd_uv, fwd, wts, total;
 };
-__host__ __device__ inline size_t bk_al(size_t x) { return (x + 15) & ~(size_t)15; }
 __host__ __device__ inline BkLayout bk_layout(int DD, int T) {
   BkLayout L;
   L.S = BK_S;
@@ -618,30 +200,17 @@ __host__ __device__ inline BkLayout bk_layout(int DD, int T) {
   off += bk_al(sizeof(double) * 80);
   L.uni = off;                                  // union: JAC scratch | U, VT + FWD scratch
   const int jnc = 16 * (DD + 1);
-  const size_t jac = bk_al(2 * sizeof(uint16_t) * jnc * BK_LD) + bk_al(sizeof(float) * 16 * jnc) +
-                     bk_al(sizeof(float) * BK_NW * jnc) + bk_al(sizeof(int) * jnc);
+  const size_t jac = bk_al(2 * sizeof(uint16_t) * jnc * FC_LD) + bk_al(sizeof(float) * 16 * jnc) +
+                     bk_al(sizeof(float) * FC_NW * jnc) + bk_al(sizeof(int) * jnc);
   L.jac = L.uni;
   L.fwd_uv = L.uni;
   const size_t uv = bk_al(sizeof(float) * 2 * (size_t)T * BK_S * DD);
   L.fwd = L.uni + uv;
-  const size_t fwd = bk_al(2 * sizeof(uint16_t) * BK_S * BK_LD) + bk_al(sizeof(float) * 16 * BK_S) +
-                     bk_al(sizeof(float) * BK_NW * BK_S) + bk_al(sizeof(int) * BK_S);
+  const size_t fwd = bk_al(2 * sizeof(uint16_t) * BK_S * FC_LD) + bk_al(sizeof(float) * 16 * BK_S) +
+                     bk_al(sizeof(float) * FC_NW * BK_S) + bk_al(sizeof(int) * BK_S);
   L.wts = L.uni + bk_al(jac > uv + fwd ? jac : uv + fwd);   // the solved net's input / output layer planes
   L.total = L.wts + sizeof(u32x4) * (BK_W0_VEC + BK_WO_VEC);
   return L;
-}
-__device__ __forceinline__ Pass bk_pass(char* base, int nc) {
-  Pass p;
-  size_t off = 0;
-  p.pl0 = reinterpret_cast<uint16_t*>(base + off);
-  p.pl1 = p.pl0 + (size_t)nc * BK_LD;
-  off += bk_al(2 * sizeof(uint16_t) * nc * BK_LD);
-  p.tmp = reinterpret_cast<float*>(base + off);
-  off += bk_al(sizeof(float) * 16 * nc);
-  p.wmax = reinterpret_cast<float*>(base + off);
-  off += bk_al(sizeof(float) * BK_NW * nc);
-  p.sx = reinterpret_cast<int*>(base + off);
-  return p;
 }
 
 enum { V_XEMB = 0, V_FX, V_XIN, V_X, V_G, V_DX, V_DG, V_XLOW, V_FLOW, V_FCUR, V_XP, V_FP, V_COUNT };
@@ -661,7 +230,7 @@ __device__ __forceinline__ void bk_jacobian(const FcArgs& a, char* jbase, const 
   const float* bias = a.L[NH + 1].b;
   bk_sync();                                   // the caller's per-sample inputs
   for (int q = 0; q < BK_FCB; ++q) {
-    for (int i = tid; i < 16 * NC; i += BK_NT) {
+    for (int i = tid; i < 16 * NC; i += FC_NT) {
       const int k = i / NC, c = i - k * NC;
       const int cb = c >> 4, sl = c & 15;
       const int s = 16 * q + sl;
@@ -689,7 +258,7 @@ __device__ __forceinline__ void bk_jacobian(const FcArgs& a, char* jbase, const 
 }
 
 template <int DD, int ACT, int NH>
-__global__ __launch_bounds__(BK_NT) void fcblock_kernel(FcBlockArgs a) {
+__global__ __launch_bounds__(FC_NT) void fcblock_kernel(FcBlockArgs a) {
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const BkLayout Ly = bk_layout(DD, a.T);
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -719,7 +288,7 @@ __global__ __launch_bounds__(BK_NT) void fcblock_kernel(FcBlockArgs a) {
   // instruction cache)
   for (int jp = 0; jp < 2; ++jp) {
   if (jp == 0) {
-    for (int i = tid; i < S * DD; i += BK_NT) {
+    for (int i = tid; i < S * DD; i += FC_NT) {
       const int s = i / DD, k = i - s * DD;
       const long b = b0 + s;
       float v = 0.f;
@@ -730,7 +299,7 @@ __global__ __launch_bounds__(BK_NT) void fcblock_kernel(FcBlockArgs a) {
       V(V_XIN)[i] = v;
     }
   } else {
-    for (int i = tid; i < S * DD; i += BK_NT) {
+    for (int i = tid; i < S * DD; i += FC_NT) {
       const int s = i / DD;
       const long b = b0 + s;
       const float v = (V(V_FX)[i] - V(V_FLOW)[i]) + V(V_XIN)[i];
@@ -1026,88 +595,6 @@ __global__ __launch_bounds__(BK_NT) void fcblock_kernel(FcBlockArgs a) {
   }  // jp
 }
 
-// ---- the power-series log-det of a fused fc net pair (basic_logdet_estimator, implicit_block.py:418-426) ----------------
-// Workgroup (blockIdx.x, net blockIdx.y) owns 48 samples: one forward pass of f at x keeps act' of every hidden unit in
-// registers (SV_SAVE), then term k = 1 .. n: v <- v^T J_f(x) as one pass of the transposed net over the 48 columns
-// (SV_VJP: the hidden epilogue multiplies by the saved derivatives), tr_k = v . eps (fp64 sum of the d products), and
-// logdet += fl(c_k * (float) tr_k) in fp32 in k order (launch_series_combine's arithmetic).  The operands stay in LDS and
-// registers between terms; the only global traffic is x, eps, the out row and the weight planes (L2-resident).
-constexpr int FS_LDS = 2 * 2 * BK_S * BK_LD + 4 * 16 * BK_S + 4 * BK_NW * BK_S + 4 * BK_S + 64;
-template <int DD, int ACT, int NH>
-__global__ __launch_bounds__(BK_NT) void fcseries_kernel(FcSeriesArgs a) {
-  __shared__ __attribute__((aligned(16))) char lds[FS_LDS];
-  const int tid = threadIdx.x, net = blockIdx.y;
-  const long b0 = (long)blockIdx.x * BK_S;
-  const int B = a.B;
-  const Pass P = bk_pass(lds, BK_S);
-  const float* x = a.x[net];
-  const float* ep = a.eps[net];
-  for (int i = tid; i < 16 * BK_S; i += BK_NT) {
-    const int k = i / BK_S, c = i - k * BK_S;
-    P.tmp[i] = (k < DD && b0 + c < B) ? x[(b0 + c) * DD + k] : 0.f;
-  }
-  Derivs<NH, BK_FCB> D;
-  mlp_pass<DD, BK_FCB, false, ACT, NH, false, SV_SAVE>(a.f[net], nullptr, P, nullptr, &D);
-  float ev[DD];
-  const bool mine = tid < BK_S && b0 + tid < B;
-#pragma unroll
-  for (int i = 0; i < DD; ++i) ev[i] = mine ? ep[(b0 + tid) * DD + i] : 0.f;
-  for (int i = tid; i < 16 * BK_S; i += BK_NT) {   // after mlp_pass's last barrier: nobody reads f(x)
-    const int k = i / BK_S, c = i - k * BK_S;
-    P.tmp[i] = (k < DD && b0 + c < B) ? ep[(b0 + c) * DD + k] : 0.f;
-  }
-  float acc = 0.f;
-  for (int k = 0; k < a.n_terms; ++k) {
-    mlp_pass<DD, BK_FCB, false, ACT, NH, false, SV_VJP>(a.t[net], nullptr, P, nullptr, &D);
-    if (tid < BK_S) {      // rows >= DD of the VJP are zero (the transposed output planes' padding rows)
-      double tr = 0.0;
-#pragma unroll
-      for (int i = 0; i < DD; ++i) tr += (double)P.tmp[i * BK_S + tid] * (double)ev[i];
-      acc = acc + a.coeff[k] * (float)tr;
-    }
-  }
-  if (mine) a.out[net][b0 + tid] = acc;
-}
-
-int fcseries_supported(const FcSeriesArgs& a) {
-  if (a.nn < 1 || a.nn > 2 || a.B <= 0 || a.n_terms < 1 || a.n_terms > 128) return 0;
-  const int nh = a.nl - 2;
-  if (!((a.d == 6 && nh == 3) || (a.d == 2 && nh == 1))) return 0;
-  if (a.act != ACT_SIN && a.act != ACT_SWISH) return 0;
-  for (int i = 0; i < a.nn; ++i) {
-    if (!a.x[i] || !a.eps[i] || !a.out[i]) return 0;
-    for (int l = 0; l < a.nl; ++l)
-      if (!a.f[i].L[l].Ah || !a.f[i].L[l].Aexp || !a.t[i].L[l].Ah || !a.t[i].L[l].Aexp) return 0;
-    if (!a.f[i].L[0].A || !a.t[i].L[0].A) return 0;             // the input layers' fp32 rows
-  }
-  return 1;
-}
-
-int launch_fcseries(const FcSeriesArgs& a, hipStream_t s) {
-  if (!fcseries_supported(a)) return INF_ERR_UNSUPPORTED;
-  const int nh = a.nl - 2;
-  const dim3 grid((unsigned)fcblock_grid(a.B), (unsigned)a.nn);
-  const bool prof = prof_enabled();
-  if (prof) prof_begin_launch(s);
-#define FS_GO(DD_, ACT_, NH_) hipLaunchKernelGGL((fcseries_kernel<DD_, ACT_, NH_>), grid, dim3(BK_NT), 0, s, a)
-  if (a.d == 6 && nh == 3) {
-    if (a.act == ACT_SIN) FS_GO(6, ACT_SIN, 3);
-    else FS_GO(6, ACT_SWISH, 3);
-  } else {
-    if (a.act == ACT_SIN) FS_GO(2, ACT_SIN, 1);
-    else FS_GO(2, ACT_SWISH, 1);
-  }
-#undef FS_GO
-  INF_CHECK_LAUNCH();
-  if (prof) {
-    // flops: the forward pass and n_terms transposed passes per sample and net
-    const double per_eval = 2.0 * a.d * FC_H * 2 + (double)nh * 2.0 * FC_H * FC_H;
-    const double f = per_eval * a.B * a.nn * (1.0 + a.n_terms);
-    prof_end_launch(s, 620, f, 4.0 * a.B * a.nn * (3.0 * a.d + 1.0), 3.0 * f / PEAK_BF16_FLOPS_PER_MS);
-  }
-  return INF_OK;
-}
-
 size_t fcblock_lds_bytes(int d, int T) { return bk_layout(d, T).total; }
 
 int fcblock_supported(const FcBlockArgs& a) {
@@ -1115,10 +602,7 @@ int fcblock_supported(const FcBlockArgs& a) {
   if (a.nx.nl != a.nz.nl || a.nx.d != a.nz.d || a.nx.act != a.nz.act) return 0;
   for (int l = 0; l < a.nx.nl; ++l)
     if (!a.nx.L[l].Ah || !a.nz.L[l].Ah) return 0;
-  const int d = a.nx.d, nh = a.nx.nl - 2;
-  if (!((d == 6 && nh == 3) || (d == 2 && nh == 1))) return 0;
-  if (a.nx.act != ACT_SIN && a.nx.act != ACT_SWISH) return 0;
-  return 1;
+  return fc_block_instance(a.nx.d, a.nx.nl - 2, a.nx.act);
 }
 
 int fcblock_grid(int B) { return (B + BK_S - 1) / BK_S; }
@@ -1129,14 +613,9 @@ int launch_fcblock(const FcBlockArgs& a, hipStream_t s) {
   const size_t lds = fcblock_lds_bytes(d, a.T);
   const unsigned nb = (unsigned)fcblock_grid(a.B);
   const void* fn = nullptr;
-#define BK_PICK(DD_, ACT_, NH_) fn = reinterpret_cast<const void*>(&fcblock_kernel<DD_, ACT_, NH_>)
-  if (d == 6 && nh == 3) {
-    if (a.nx.act == ACT_SIN) BK_PICK(6, ACT_SIN, 3);
-    else BK_PICK(6, ACT_SWISH, 3);
-  } else {
-    if (a.nx.act == ACT_SIN) BK_PICK(2, ACT_SIN, 1);
-    else BK_PICK(2, ACT_SWISH, 1);
-  }
+#define BK_PICK(DD_, ACT_, NH_) \
+  if (d == DD_ && a.nx.act == ACT_ && nh == NH_) fn = reinterpret_cast<const void*>(&fcblock_kernel<DD_, ACT_, NH_>);
+  FC_BLOCK_INSTANCES(BK_PICK)
 #undef BK_PICK
   // dynamic LDS beyond the default limit: raised per kernel to what this launch needs (static LDS + dynamic <= 160 KiB)
   static thread_local std::pair<const void*, size_t> attr_set[6] = {};
@@ -1161,9 +640,9 @@ int launch_fcblock(const FcBlockArgs& a, hipStream_t s) {
   const bool prof = prof_enabled();
   if (prof) prof_begin_launch(s);
   if (a.per_sample) {
-    INF_HIP(hipLaunchKernel(fn, dim3(nb), dim3(BK_NT), kargs, lds, s));
+    INF_HIP(hipLaunchKernel(fn, dim3(nb), dim3(FC_NT), kargs, lds, s));
   } else {
-    const hipError_t e = hipLaunchCooperativeKernel(fn, dim3(nb), dim3(BK_NT), kargs, (unsigned)lds, s);
+    const hipError_t e = hipLaunchCooperativeKernel(fn, dim3(nb), dim3(FC_NT), kargs, (unsigned)lds, s);
     if (e == hipErrorCooperativeLaunchTooLarge) {
       (void)hipGetLastError();
       return INF_ERR_UNSUPPORTED;
@@ -1194,11 +673,14 @@ int launch_fcblock(const FcBlockArgs& a, hipStream_t s) {
   if (prof) {
     // flops: the two Jacobians and f(0) (the solve's later evaluations depend on its step count, which the caller
     // reads from the statistics)
-    const double per_eval = 2.0 * d * FC_H * 2 + (double)nh * 2.0 * FC_H * FC_H;
-    const double f = per_eval * a.B * (2.0 * (d + 1) + 1.0);
+    const double f = fc_flops_per_column(d, a.nx.nl) * a.B * (2.0 * (d + 1) + 1.0);
     prof_end_launch(s, 610, f, 4.0 * a.B * d * 4.0, 3.0 * f / PEAK_BF16_FLOPS_PER_MS);
   }
   return INF_OK;
 }
 
 }  // namespace inf
+
+// The series kernel is compiled in this translation unit: on its own the same source gets another register allocation
+// (DESIGN.md section 24), and its machine code is held to the parent's.
+#include "fcseries.inc"

@@ -339,8 +339,7 @@ int launch_fcnet(const FcArgs& a, bool jac, hipStream_t s) {
 #undef FCL1
   if (prof) {
     const double T = jac ? a.d + 1 : 1;
-    double f = 2.0 * a.d * FC_H * 2 + (double)(a.nl - 2) * 2.0 * FC_H * FC_H;   // per sample and column
-    f *= T * a.B;
+    const double f = fc_flops_per_column(a.d, a.nl) * T * a.B;
     // MFMA instruction time at the dense peak: exact fp32 1 per algorithmic FLOP; f16x3 3 fp16 products (fcnet_h3.hip)
     const double pk = h3 ? 3.0 * f / PEAK_BF16_FLOPS_PER_MS : f / PEAK_F32_FLOPS_PER_MS;
     prof_end_launch(s, jac ? 601 : 600, f, 4.0 * a.B * a.d * (jac ? 2.0 : 3.0), pk);
@@ -356,7 +355,7 @@ int launch_fcnet_jac_pair(const FcArgs& a0, const FcArgs& a1, hipStream_t s) {
   INF_TRY(launch_fcnet_h3_jac_pair(a0, a1, s));
   if (prof) {
     const double T = a0.d + 1;
-    const double f = (2.0 * a0.d * FC_H * 2 + (double)(a0.nl - 2) * 2.0 * FC_H * FC_H) * T * (a0.B + a1.B);
+    const double f = fc_flops_per_column(a0.d, a0.nl) * T * (a0.B + a1.B);
     prof_end_launch(s, 602, f, 4.0 * (a0.B + a1.B) * a0.d * 2.0, 3.0 * f / PEAK_BF16_FLOPS_PER_MS);
   }
   return INF_OK;

@@ -1,12 +1,18 @@
-// Shared by the fused fc kernels (fcnet.hip: exact fp32 MFMA; fcnet_h3.hip: scaled two-piece fp16).
+// Shared by the fused fc kernels (fcnet.hip: exact fp32 MFMA; fcnet_h3.hip: scaled two-piece fp16; fc_h3_ops.h and
+// fcblock_pass.h build on it): the in-kernel Broyden update, the LU log-det, the exact input layer, the activations,
+// the host dispatch by activation.
 #pragma once
 
 #include "kernels.h"
+#include "pointwise_ops.h"
 
 namespace inf {
 
 constexpr int FC_H = 128;      // hidden width of the fused nets
 constexpr int FC_DMAX = 16;
+
+// flops of one evaluation of a fused net (d in and out, nl layers, 128 wide between) on one column, for the profile
+inline double fc_flops_per_column(int d, int nl) { return 2.0 * d * FC_H * 2 + (double)(nl - 2) * 2.0 * FC_H * FC_H; }
 
 // The Broyden update of sample b (broyden.hip broyden_small_kernel / broyden_small_d_kernel: the same sums in the
 // same order and precision) for the fused update + residual launch: x_new also goes to the net's input column
@@ -82,8 +88,7 @@ __device__ __forceinline__ void broyden_update_fc(const BroydenArgs& a, long b, 
 #pragma unroll
   for (int i = 0; i < N; ++i) {
     float u = um[i] / denf;
-    if (vt[i] != vt[i]) vt[i] = 0.f;
-    if (u != u) u = 0.f;
+    scrub_nan(vt[i], u);
     um[i] = u;
     if (i < d) {
       Vm[E(i)] = vt[i];
@@ -127,10 +132,9 @@ __device__ __forceinline__ void broyden_update_fc(const BroydenArgs& a, long b, 
     if (i >= d) continue;
     const float up = -tt[i];
     a.upd[E(i)] = up;
-    const float x0 = a.x[E(i)];
-    const float xe = x0 + up;
+    float xe;
+    broyden_step(a.x[E(i)], up, xe, a.dxnew[E(i)]);
     a.xnew[E(i)] = xe;
-    a.dxnew[E(i)] = xe - x0;
     in[i * ld] = xe;
     xn[i] = xe;
     gxo[i] = gx[i];

@@ -18,57 +18,17 @@
 // 136 halves + 16 x 112 fp32 staging / output rows + the column maxima: 72 KiB, two workgroups per CU.
 #include <type_traits>
 
-#include "fcnet_common.h"
+#include "fc_h3_ops.h"
 #include "pointwise_ops.h"
 
 namespace inf {
-
-namespace {
-constexpr int H3_NW = 8;
-constexpr int H3_NT = 64 * H3_NW;
-constexpr int H3_LD = FC_H + 8;      // halves per activation-plane column (272 B: 16-byte aligned, spreads the banks)
-
-__device__ __forceinline__ f32x4 mfma3(const u32x4 (&a)[2], const u32x4& xh, const u32x4& xl, f32x4 c) {
-  const f16x8 ah = __builtin_bit_cast(f16x8, a[0]), al = __builtin_bit_cast(f16x8, a[1]);
-  const f16x8 bh = __builtin_bit_cast(f16x8, xh), bl = __builtin_bit_cast(f16x8, xl);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, c, 0, 0, 0);
-  return c;
-}
-
-// the (h, l) fragments of row tile rt, k steps [0, NKS), of a layer's planes (fragment tile (rt nks + ks): 2 x 512 halves)
-template <int NKS>
-__device__ __forceinline__ void ldw_h3(const uint16_t* A, int nks, int rt, int lane, u32x4 (&w)[NKS][2]) {
-  const u32x4* p = reinterpret_cast<const u32x4*>(A);
-#pragma unroll
-  for (int ks = 0; ks < NKS; ++ks) {
-    const long t = (long)rt * nks + ks;
-    w[ks][0] = p[(t * 2 + 0) * 64 + lane];
-    w[ks][1] = p[(t * 2 + 1) * 64 + lane];
-  }
-}
-
-// 4 fp32 values (consecutive rows of one column) -> scaled fp16 h / l pieces, packed
-__device__ __forceinline__ void split4(const float (&v)[4], float S, uint2& h, uint2& l) {
-  _Float16 hh[4], ll[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    hh[r] = (_Float16)(v[r] * S);
-    ll[r] = (_Float16)__builtin_fmaf(v[r], S, -(float)hh[r]);
-  }
-  const f16x2 a = {hh[0], hh[1]}, b = {hh[2], hh[3]}, c = {ll[0], ll[1]}, e = {ll[2], ll[3]};
-  h = make_uint2(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b));
-  l = make_uint2(__builtin_bit_cast(unsigned, c), __builtin_bit_cast(unsigned, e));
-}
-}  // namespace
 
 // DD: the FWD kernels' d at compile time for the in-kernel Broyden update (0: runtime); bid: the workgroup's sample block
 template <int NCB, bool JAC, int ACT, int DD>
 __device__ __forceinline__ void fcnet_h3_body(const FcArgs& a, long bid) {
   constexpr int NC = 16 * NCB;
   constexpr int S = JAC ? 16 : NC;
-  static_assert(NCB <= H3_NW, "one output column block per wave");
+  static_assert(NCB <= FC_NW, "one output column block per wave");
   // Sin nets: every hidden activation is in [-1 / (2 pi), 1 / (2 pi)], so one power-of-two scale 2^SFIX puts every
   // value below 2^15 (no fp16 overflow) and the split keeps 22 bits of each value down to |v| ~ 2^-20 (below, the low
   // piece is subnormal: an absolute error under 2^-41).  The FWD needs no column maxima then (their exchange across
@@ -84,10 +44,10 @@ __device__ __forceinline__ void fcnet_h3_body(const FcArgs& a, long bid) {
   constexpr int SFIX = FC_SFIX;
   constexpr int SFIXT = FC_SFIXT;
   constexpr int NBUF = FIXS ? 2 : 1;
-  __shared__ __attribute__((aligned(16))) uint16_t pl[NBUF][2][NC * H3_LD];   // activation planes h, l: [col][k]
+  __shared__ __attribute__((aligned(16))) uint16_t pl[NBUF][2][NC * FC_LD];   // activation planes h, l: [col][k]
   int cur = 0;                                                              // the buffer holding the layer input
   __shared__ __attribute__((aligned(16))) float tmp[16 * NC];           // input rows / output rows (fp32, [row][col])
-  __shared__ float wmax[H3_NW][NC];
+  __shared__ float wmax[FC_NW][NC];
   __shared__ int sx[NC];                                                // the planes' column scale exponents
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 15, g = lane >> 4;
@@ -96,7 +56,7 @@ __device__ __forceinline__ void fcnet_h3_body(const FcArgs& a, long bid) {
   const bool br_on = !JAC && a.br_on;
 
   // ---- input rows [0, 16) in fp32: x (primal), e_j (JAC tangent block j); br_on: rows [0, d) from the update below
-  for (int i = tid; i < 16 * NC; i += H3_NT) {
+  for (int i = tid; i < 16 * NC; i += FC_NT) {
     const int k = i / NC, c = i - k * NC;
     const int cb = c >> 4, sl = JAC ? (c & 15) : c;
     const long b = b0 + sl;
@@ -164,8 +124,8 @@ __device__ __forceinline__ void fcnet_h3_body(const FcArgs& a, long bid) {
 #pragma unroll
         for (int cb = 0; cb < NCB; ++cb) {
           const int col = cb * 16 + li;
-          const u32x4 xh = *reinterpret_cast<const u32x4*>(inh + col * H3_LD + ks * 32 + 8 * g);
-          const u32x4 xl = *reinterpret_cast<const u32x4*>(inl + col * H3_LD + ks * 32 + 8 * g);
+          const u32x4 xh = *reinterpret_cast<const u32x4*>(inh + col * FC_LD + ks * 32 + 8 * g);
+          const u32x4 xl = *reinterpret_cast<const u32x4*>(inl + col * FC_LD + ks * 32 + 8 * g);
           acc[cb] = mfma3(wr[ks], xh, xl, acc[cb]);
         }
       const int sw = ldc(L.Aexp);
@@ -176,18 +136,7 @@ __device__ __forceinline__ void fcnet_h3_body(const FcArgs& a, long bid) {
         for (int r = 0; r < 4; ++r) v[cb][r] = __builtin_amdgcn_ldexpf(acc[cb][r], e);
       }
     }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      if constexpr (JAC) {
-        float dd;
-        fc_act_fd<ACT>(v[0][r] + bias[r], sp, v[0][r], dd);
-#pragma unroll
-        for (int cb = 1; cb < NCB; ++cb) v[cb][r] *= dd;
-      } else {
-#pragma unroll
-        for (int cb = 0; cb < NCB; ++cb) v[cb][r] = fc_act_f<ACT>(v[cb][r] + bias[r], sp);
-      }
-    }
+    h3_epilogue<JAC ? EP_JAC : EP_ACT, ACT, NCB>(v, [&](int r) { return bias[r]; }, sp);
     if constexpr (FIXS) {
       // the other buffer: no wave reads it in this layer, and the barrier below orders it before the next layer
       const int nb = cur ^ 1;
@@ -197,8 +146,8 @@ __device__ __forceinline__ void fcnet_h3_body(const FcArgs& a, long bid) {
         const int col = cb * 16 + li;
         uint2 h, lo;
         split4(v[cb], Sf, h, lo);
-        *reinterpret_cast<uint2*>(pl[nb][0] + col * H3_LD + 16 * w + 4 * g) = h;
-        *reinterpret_cast<uint2*>(pl[nb][1] + col * H3_LD + 16 * w + 4 * g) = lo;
+        *reinterpret_cast<uint2*>(pl[nb][0] + col * FC_LD + 16 * w + 4 * g) = h;
+        *reinterpret_cast<uint2*>(pl[nb][1] + col * FC_LD + 16 * w + 4 * g) = lo;
       }
       __syncthreads();
       cur = nb;
@@ -210,8 +159,8 @@ __device__ __forceinline__ void fcnet_h3_body(const FcArgs& a, long bid) {
         const int e = cb == 0 ? SFIX : SFIXT;
         uint2 h, lo;
         split4(v[cb], __builtin_amdgcn_ldexpf(1.f, e), h, lo);
-        *reinterpret_cast<uint2*>(pl[0][0] + col * H3_LD + 16 * w + 4 * g) = h;
-        *reinterpret_cast<uint2*>(pl[0][1] + col * H3_LD + 16 * w + 4 * g) = lo;
+        *reinterpret_cast<uint2*>(pl[0][0] + col * FC_LD + 16 * w + 4 * g) = h;
+        *reinterpret_cast<uint2*>(pl[0][1] + col * FC_LD + 16 * w + 4 * g) = lo;
         if (w == 0 && g == 0) sx[col] = e;
       }
       __syncthreads();
@@ -230,12 +179,12 @@ __device__ __forceinline__ void fcnet_h3_body(const FcArgs& a, long bid) {
         const int col = cb * 16 + li;
         float m = 0.f;
 #pragma unroll
-        for (int ww = 0; ww < H3_NW; ++ww) m = fmaxf(m, wmax[ww][col]);
+        for (int ww = 0; ww < FC_NW; ++ww) m = fmaxf(m, wmax[ww][col]);
         const int e = (SIN && cb == 0) ? SFIX : h3_scale_exp(m);   // (JAC: the primal column as the FWD kernel)
         uint2 h, lo;
         split4(v[cb], __builtin_amdgcn_ldexpf(1.f, e), h, lo);
-        *reinterpret_cast<uint2*>(pl[0][0] + col * H3_LD + 16 * w + 4 * g) = h;
-        *reinterpret_cast<uint2*>(pl[0][1] + col * H3_LD + 16 * w + 4 * g) = lo;
+        *reinterpret_cast<uint2*>(pl[0][0] + col * FC_LD + 16 * w + 4 * g) = h;
+        *reinterpret_cast<uint2*>(pl[0][1] + col * FC_LD + 16 * w + 4 * g) = lo;
         if (w == 0 && g == 0) sx[col] = e;
       }
       __syncthreads();
@@ -269,16 +218,7 @@ __device__ __forceinline__ void fcnet_h3_body(const FcArgs& a, long bid) {
     u32x4 wo[4][2];
     ldw_h3<4>(L.Ah, 4, 0, lane, wo);
     const int col = w * 16 + li;
-    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      const u32x4 xh = *reinterpret_cast<const u32x4*>(pl[cur][0] + col * H3_LD + ks * 32 + 8 * g);
-      const u32x4 xl = *reinterpret_cast<const u32x4*>(pl[cur][1] + col * H3_LD + ks * 32 + 8 * g);
-      acc = mfma3(wo[ks], xh, xl, acc);
-    }
-    const int e = -(ldc(L.Aexp) + (FIXS ? SFIX : sx[col]));
-#pragma unroll
-    for (int r = 0; r < 4; ++r) tmp[(4 * g + r) * NC + col] = __builtin_amdgcn_ldexpf(acc[r], e);
+    h3_out_layer<FC_LD>(wo, L.Aexp, pl[cur][0], pl[cur][1], col, g, [&]() { return FIXS ? SFIX : sx[col]; }, tmp, NC);
   }
   __syncthreads();
   auto fsum = [&](int row, int c) { return tmp[row * NC + c]; };   // the output layer's value (no bias)
@@ -349,12 +289,12 @@ __device__ __forceinline__ void fcnet_h3_body(const FcArgs& a, long bid) {
 }
 
 template <int NCB, bool JAC, int ACT, int DD>
-__global__ __launch_bounds__(H3_NT) void fcnet_h3_kernel(FcArgs a) {
+__global__ __launch_bounds__(FC_NT) void fcnet_h3_kernel(FcArgs a) {
   fcnet_h3_body<NCB, JAC, ACT, DD>(a, blockIdx.x);
 }
 // two JAC launches of the same shape in one grid (launch_fcnet_jac_pair): workgroups [0, nb0) run p.a[0]
 template <int NCB, int ACT>
-__global__ __launch_bounds__(H3_NT) void fcnet_h3_pair_kernel(FcPair p) {
+__global__ __launch_bounds__(FC_NT) void fcnet_h3_pair_kernel(FcPair p) {
   const int sel = (int)blockIdx.x >= p.nb0 ? 1 : 0;
   fcnet_h3_body<NCB, true, ACT, 0>(p.a[sel], (long)blockIdx.x - (sel ? p.nb0 : 0));
 }
@@ -363,27 +303,16 @@ constexpr int FC_FWD_NCB = 3;   // column blocks per workgroup of the FWD kernel
 int launch_fcnet_h3(const FcArgs& a, bool jac, hipStream_t s) {
   const int S = jac ? 16 : 16 * FC_FWD_NCB;
   const unsigned nb = (unsigned)((a.B + S - 1) / S);
-#define FCH1(ACT_, NCB_, JAC_, DD_) \
-  hipLaunchKernelGGL((fcnet_h3_kernel<NCB_, JAC_, ACT_, DD_>), dim3(nb), dim3(H3_NT), 0, s, a)
-#define FCH(NCB_, JAC_, DD_) FC_BY_ACT(a.act, FCH1, NCB_, JAC_, DD_)
   // FWD whose readback event completes with the launch itself (OutArgs::stop_ev; not while profiling, whose events
   // bracket every launch)
   const bool bind = !jac && a.o.stop_ev && !prof_enabled();
-#define FCE1(ACT_, NCB_, DD_)                                                                                   \
-  hipExtLaunchKernelGGL((fcnet_h3_kernel<NCB_, false, ACT_, DD_>), dim3(nb), dim3(H3_NT), 0, s, nullptr, a.o.stop_ev, \
-                        0, a)
-#define FCE(NCB_, DD_) FC_BY_ACT(a.act, FCE1, NCB_, DD_)
-  if (bind) {
-    if (a.d == 6) FCE(FC_FWD_NCB, 6);
-    else if (a.d == 2) FCE(FC_FWD_NCB, 2);
-    else if (a.d == 8) FCE(FC_FWD_NCB, 8);
-    else FCE(FC_FWD_NCB, 0);
-    INF_CHECK_LAUNCH();
-    *a.o.stop_bound = true;
-    return INF_OK;
-  }
-#undef FCE
-#undef FCE1
+#define FCH1(ACT_, NCB_, JAC_, DD_)                                                                \
+  do {                                                                                             \
+    const auto kern = fcnet_h3_kernel<NCB_, JAC_, ACT_, DD_>;                                      \
+    if (bind) hipExtLaunchKernelGGL(kern, dim3(nb), dim3(FC_NT), 0, s, nullptr, a.o.stop_ev, 0, a); \
+    else hipLaunchKernelGGL(kern, dim3(nb), dim3(FC_NT), 0, s, a);                                 \
+  } while (0)
+#define FCH(NCB_, JAC_, DD_) FC_BY_ACT(a.act, FCH1, NCB_, JAC_, DD_)
   if (!jac) {
     if (a.d == 6) FCH(FC_FWD_NCB, false, 6);
     else if (a.d == 2) FCH(FC_FWD_NCB, false, 2);
@@ -397,6 +326,7 @@ int launch_fcnet_h3(const FcArgs& a, bool jac, hipStream_t s) {
 #undef FCH
 #undef FCH1
   INF_CHECK_LAUNCH();
+  if (bind) *a.o.stop_bound = true;
   return INF_OK;
 }
 
@@ -406,7 +336,7 @@ int launch_fcnet_h3_jac_pair(const FcArgs& a0, const FcArgs& a1, hipStream_t s) 
   p.a[1] = a1;
   p.nb0 = (a0.B + 15) / 16;
   const unsigned nb = (unsigned)(p.nb0 + (a1.B + 15) / 16);
-#define FCP1(ACT_, NCB_) hipLaunchKernelGGL((fcnet_h3_pair_kernel<NCB_, ACT_>), dim3(nb), dim3(H3_NT), 0, s, p)
+#define FCP1(ACT_, NCB_) hipLaunchKernelGGL((fcnet_h3_pair_kernel<NCB_, ACT_>), dim3(nb), dim3(FC_NT), 0, s, p)
 #define FCP(NCB_) FC_BY_ACT(a0.act, FCP1, NCB_)
   if (a0.d == 2) FCP(3);
   else FCP(7);
